@@ -19,7 +19,13 @@ Two launch modes, one frame:
   its planned tiles (plan from rank 0, broadcast), one torch.distributed gather (backend
   nccl = RCCL over xGMI) to rank 0, which unpacks; the time is the max over ranks.
 
-Rank 0 prints ONE JSON line with, beside the contract's fields:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line;
+its parity, cpu_baseline and roofline fields are null.  --dump-outputs DIR writes what the last
+timed step computed: DIR/frame.npy (the float32 H x W x 3 frame) and DIR/counters.npy (that
+frame's device counters, float64, in grayshift_amd._native.COUNTER_NAMES order).  The scene, the
+seed and so the frame are the same from run to run with the same arguments.
+
+With --full, rank 0's ONE JSON line carries, beside the contract's fields:
 * parity — the timed frame checked against the CPU oracle (the reference's algorithm
   restated, oracle/) on a deterministic pixel subset, at the full config;
 * cpu_baseline — at N=1 the oracle's render time on that subset (median of 3, world and
@@ -120,10 +126,15 @@ def parse():
     ap.add_argument("--parity-stride", type=int, default=12, help="parity subset at N>1: every Nth row and column")
     ap.add_argument("--cpu-runs", type=int, default=3, help="CPU baseline: median of this many renders")
     ap.add_argument("--cpu-threads", type=int, default=None)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and the parity check")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline and the parity check")
     ap.add_argument("--pmc-dir", default=os.path.join(ROOT, "profiles", "pmc"),
                     help="PMC summaries (tools/pmc_summary.py), matched by code-object hash and config")
     ap.add_argument("--dump", default=None, help="write the frame (rank 0) as .npy")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's frame and counters as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity check against the CPU oracle, the CPU baseline and the roofline "
+                         "(off by default: a plain run times the steps and prints the line)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collectives: nccl (= RCCL over xGMI, the measured path) or gloo (host-staged; testing)")
     ap.add_argument("--gather", action="store_true",
@@ -188,7 +199,7 @@ def main_context(a):
     sync_all()
     elapsed = time.perf_counter() - t0
     kms = [st.kernel_ms_max for st in stats]
-    tot = None
+    tot = cd = None
     for st in stats:
         cd = st.counters.as_dict()
         tot = cd if tot is None else {k: tot[k] + v for k, v in cd.items()}
@@ -196,7 +207,7 @@ def main_context(a):
     d_rgb, dev0 = m.frame_ptr()
     img = np.zeros((m.height, m.width, 3), dtype=np.float32)
     N.check(N.lib.gs_device_download(img.ctypes.data, C.c_void_p(d_rgb), img.nbytes))
-    emit(a, sc, m, c, elapsed, sum(kms) / len(kms), img, a.gpus,
+    emit(a, sc, m, c, cd, elapsed, sum(kms) / len(kms), img, a.gpus,
          {"tile_plan": "cost-balanced" if plan else "round-robin",
           "collective": "rccl" if a.gpus > 1 else "none",
           "launch": "one process, %d device(s): gs_multi_create once, gs_multi_render per frame" % a.gpus})
@@ -310,6 +321,8 @@ def main_ranks(a, world):
     tot_c = tot.to(cdev)
     dist.all_reduce(tot_c, op=dist.ReduceOp.SUM)
     tot = tot_c.to(dev)
+    last_c = counters.to(cdev)  # the last timed frame's, summed over the ranks
+    dist.all_reduce(last_c, op=dist.ReduceOp.SUM)
     km = torch.tensor([sum(kms) / len(kms)], dtype=torch.float64, device=cdev)
     dist.all_reduce(km, op=dist.ReduceOp.MAX)
     kernel_avg_ms = float(km.item())
@@ -318,7 +331,8 @@ def main_ranks(a, world):
     c = {n: int(tot[i].item()) // a.steps for i, n in enumerate(COUNTER_NAMES)}
     if rank == 0:
         img = frame.view(r.height, r.width, 3).cpu().numpy()
-        emit(a, sc, r, c, elapsed, kernel_avg_ms, img, world,
+        last = {n: int(last_c[i].item()) for i, n in enumerate(COUNTER_NAMES)}
+        emit(a, sc, r, c, last, elapsed, kernel_avg_ms, img, world,
              {"tile_plan": "cost-balanced" if plan else "round-robin",
               "collective": "rccl" if a.backend == "nccl" else "gloo",
               "launch": "torch.distributed.run: %d process(es), one GPU each" % world})
@@ -326,15 +340,27 @@ def main_ranks(a, world):
     r.close()
 
 
-def emit(a, sc, r, c, elapsed, kernel_avg_ms, img, world, launch_info):
-    """Rank 0's JSON line (kernel_avg_ms: the render launch of the slowest GPU, per frame)."""
+def dump_outputs(out_dir, img, last):
+    """--dump-outputs: the last timed step's frame and counters, one .npy each."""
+    import numpy as np
+    from grayshift_amd._native import COUNTER_NAMES
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), np.ascontiguousarray(img, dtype=np.float32))
+    np.save(os.path.join(out_dir, "counters.npy"), np.array([last[n] for n in COUNTER_NAMES], dtype=np.float64))
+
+
+def emit(a, sc, r, c, last, elapsed, kernel_avg_ms, img, world, launch_info):
+    """Rank 0's JSON line (kernel_avg_ms: the render launch of the slowest GPU, per frame;
+    c: the counters' mean over the timed frames, last: the last timed frame's)."""
     import numpy as np
     rays_per_frame = c["rays"]
     value = rays_per_frame * a.steps / elapsed / 1e6
     if a.dump:
         np.save(a.dump, img)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, img, last)
     cpu = parity = None
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         stride = a.cpu_stride if world == 1 else a.parity_stride
         cpu, parity = cpu_check(sc, a, img, stride, runs=a.cpu_runs if world == 1 else 1)
         if world > 1:
@@ -365,7 +391,7 @@ def emit(a, sc, r, c, elapsed, kernel_avg_ms, img, world, launch_info):
         "dtype": "f64",
         "data": "synthetic (deterministic scene generator, seed 'grayshif'; decoded reference assets)",
         "config": cfg,
-        "roofline": roofline(a, c, world, kernel_avg_ms, invalid),
+        "roofline": roofline(a, c, world, kernel_avg_ms, invalid) if a.full else None,
         "parity": parity,
         "cpu_baseline": cpu,
     }

@@ -188,9 +188,9 @@ def test_bench_context_path_and_too_many_gpus(tmp_path):
     """bench.py without a launcher drives the devices through the frame context: its frame
     equals the one-shot render; --gpus above the visible devices fails with a message."""
     out = tmp_path / "ctx.npy"
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--no-cpu", "--width", "160",
-                        "--spp", "8", "--seed", "3", "--dump", str(out)], cwd=ROOT, capture_output=True, text=True,
-                       timeout=300)
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--width",
+                        "160", "--spp", "8", "--seed", "3", "--dump", str(out)], cwd=ROOT, capture_output=True,
+                       text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["config"]["collective"] == "none" and "gs_multi" in d["config"]["launch"]
@@ -200,6 +200,28 @@ def test_bench_context_path_and_too_many_gpus(tmp_path):
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "64", "--steps", "1", "--no-cpu"], cwd=ROOT,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "visible" in r.stderr
+
+
+def test_bench_plain_run_dumps_its_last_frame(tmp_path):
+    """A plain bench.py run (no --full) prints the line with the headline fields and leaves
+    parity / cpu_baseline / roofline null; --dump-outputs writes the last timed step's frame
+    (float32) and counters (float64, COUNTER_NAMES order), equal to the one-shot render's."""
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--width", "160",
+                        "--spp", "8", "--seed", "3", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Msamples/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f64" and d["metric"].startswith("Msamples/sec")
+    assert d["parity"] is None and d["cpu_baseline"] is None and d["roofline"] is None
+    assert sorted(os.listdir(out)) == ["counters.npy", "frame.npy"]
+    frame, counters = np.load(out / "frame.npy"), np.load(out / "counters.npy")
+    ref, rc = g.render(scenes.config("C4", width=160, spp=8), seed=3)
+    assert frame.dtype == np.float32 and np.array_equal(frame, ref)
+    assert counters.dtype == np.float64 and [int(v) for v in counters] == [rc[n] for n in N.COUNTER_NAMES]
 
 
 def test_concurrent_launches_of_one_scene():

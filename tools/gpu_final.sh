@@ -22,7 +22,7 @@ tests)
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1 || { echo "GPU TESTS FAILED"; tail -40 $O/gpu_tests.log; exit 1; }
   tail -2 $O/gpu_tests.log ;;
 bench)
-  timeout -k 10 300 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
   cat $O/bench.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --no-cpu --steps 3 --warmup 1 > $O/stats_bench.json 2> $O/stats_bench.err || { echo "stats run failed"; tail -5 $O/stats_bench.err; exit 1; }
   cat $O/stats_bench.json
@@ -40,12 +40,12 @@ pmc)
 configs)
   for spec in "C1 1 3" "C2 4 1" "C3 8 1" "C4 3 3" "C5 24 1" "A1 3 1" "A2 8 1"; do
     set -- $spec
-    timeout -k 10 600 python -u bench.py --config $1 --steps 3 --warmup 1 --cpu-stride $2 --cpu-runs $3 > $O/cfg_$1.json 2> $O/cfg_$1.err || { echo "bench $1 failed"; tail -5 $O/cfg_$1.err; exit 1; }
+    timeout -k 10 600 python -u bench.py --full --config $1 --steps 3 --warmup 1 --cpu-stride $2 --cpu-runs $3 > $O/cfg_$1.json 2> $O/cfg_$1.err || { echo "bench $1 failed"; tail -5 $O/cfg_$1.err; exit 1; }
     python -c "import json; d=json.loads(open('$O/cfg_$1.json').read().strip().splitlines()[-1]); p=d['parity']; r=d['roofline']; print('$1', d['value'], 'Msamples/s', d['ms_per_step'], 'ms', 'parity max|d| %g over %d px' % (p['max_abs_delta'], p['pixels']), 'cpu', d['cpu_baseline']['value'], 'frac', r['frac'], 'lane_frac', r.get('lane_frac'), 'useful_frac', r.get('useful_frac'))"
   done
-  timeout -k 10 300 python3 -u bench.py --config final_scene --width 1440 --spp 64 --steps 2 --warmup 1 --cpu-stride 4 --cpu-runs 1 > $O/final_scene_1440.json 2> $O/final_scene_1440.err || { echo "final_scene failed"; tail -5 $O/final_scene_1440.err; exit 1; }
+  timeout -k 10 300 python3 -u bench.py --full --config final_scene --width 1440 --spp 64 --steps 2 --warmup 1 --cpu-stride 4 --cpu-runs 1 > $O/final_scene_1440.json 2> $O/final_scene_1440.err || { echo "final_scene failed"; tail -5 $O/final_scene_1440.err; exit 1; }
   python -c "import json; d=json.loads(open('$O/final_scene_1440.json').read().strip().splitlines()[-1]); print('final_scene', d['value'], d['ms_per_step'], d['parity']['max_abs_delta'], d['cpu_baseline']['value'], d['roofline']['frac'], d['roofline'].get('lane_frac'))"
-  timeout -k 10 300 python3 -u bench.py --config cornell_smoke --width 1440 --spp 64 --steps 2 --warmup 1 --cpu-stride 4 --cpu-runs 1 > $O/cornell_smoke_1440.json 2> $O/cornell_smoke_1440.err || { echo "cornell_smoke failed"; tail -5 $O/cornell_smoke_1440.err; exit 1; }
+  timeout -k 10 300 python3 -u bench.py --full --config cornell_smoke --width 1440 --spp 64 --steps 2 --warmup 1 --cpu-stride 4 --cpu-runs 1 > $O/cornell_smoke_1440.json 2> $O/cornell_smoke_1440.err || { echo "cornell_smoke failed"; tail -5 $O/cornell_smoke_1440.err; exit 1; }
   python -c "import json; d=json.loads(open('$O/cornell_smoke_1440.json').read().strip().splitlines()[-1]); print('cornell_smoke', d['value'], d['ms_per_step'], d['parity']['max_abs_delta'], d['cpu_baseline']['value'])" ;;
 stamps)
   # every config's lane-efficiency summary (bench.py's roofline lane_frac), at the config's own

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One parameterised sweep over bench.py runs (replaces round 1's sweep*.sh / ab_variants.sh).
 
-Every combination of the given values runs `bench.py --steps S --warmup 1 --no-cpu` once,
+Every combination of the given values runs `bench.py --steps S --warmup 1 --full --no-cpu` once,
 each under its own time limit; one line per run is printed (and the JSON kept under
 gpurun_out/sweep/).  A failing run ends the sweep.
 
@@ -37,8 +37,8 @@ def main():
     axes = [a.lib, a.config] + [getattr(a, k) for k in KNOBS]
     for n, combo in enumerate(itertools.product(*axes)):
         lib, config, vals = combo[0], combo[1], combo[2:]
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", "1", "--no-cpu",
-               "--config", config]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", "1", "--full",
+               "--no-cpu", "--config", config]
         cmd += ["--width", str(a.width)] if a.width else []
         cmd += ["--spp", str(a.spp)] if a.spp else []
         for k, v in zip(KNOBS, vals):
