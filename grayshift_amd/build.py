@@ -11,6 +11,7 @@ never fuses multiply-add, and neither may we.
 Usage: python -m grayshift_amd.build [--force] [--no-oracle]
 """
 import argparse
+import glob
 import os
 import subprocess
 import sys
@@ -22,23 +23,22 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_LIB = os.path.join(ORACLE_DIR, "liboracle.so")
 
 SOURCES = [
-    os.path.join(HERE, "csrc", "device", "render.hip"),
+    os.path.join(HERE, "csrc", "device", "render.hip"),   # the kernels and their launchers
     os.path.join(HERE, "csrc", "device", "output.hip"),
+    os.path.join(HERE, "csrc", "host", "scene.cpp"),      # flat scene -> device scene
+    os.path.join(HERE, "csrc", "host", "launch.cpp"),     # device scene -> launches
     os.path.join(HERE, "csrc", "host", "world.cpp"),
     os.path.join(HERE, "csrc", "host", "camera.cpp"),
     os.path.join(HERE, "csrc", "host", "host_capi.cpp"),
     os.path.join(HERE, "csrc", "host", "multi_gpu.cpp"),
 ]
-DEPS = SOURCES + [
-    os.path.join(HERE, "csrc", "device", "devmath.hpp"),
-    os.path.join(HERE, "csrc", "device", "geometry.hpp"),
-    os.path.join(HERE, "csrc", "device", "perlin.hpp"),
-    os.path.join(HERE, "csrc", "host", "world.hpp"),
-    os.path.join(ROOT, "include", "grayshift_gpu.h"),
-    os.path.join(ROOT, "include", "grayshift_host.h"),
-    os.path.join(ROOT, "include", "grayshift_scene.h"),
-    os.path.abspath(__file__),  # the compiler flags
-]
+
+
+def _headers():
+    """Every header a source may include, and this file (the compiler flags)."""
+    return (sorted(glob.glob(os.path.join(HERE, "csrc", "**", "*.hpp"), recursive=True)) +
+            sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))) + [os.path.abspath(__file__)])
+
 
 ARCH = os.environ.get("GS_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -54,14 +54,24 @@ def _stale(target, deps):
 
 
 def build_product(force=False, verbose=False, extra=(), out=None):
-    """Build libgrayshift.so (or a variant at `out` with extra compiler flags)."""
+    """Build libgrayshift.so (or a variant at `out` with extra compiler flags).
+
+    Nothing is done while the library is newer than every source, every header and this file
+    (a tree that was copied with its library but without its objects stays as it is).  Else a
+    source is compiled only when its object is missing or older than the source, any header
+    or this file; `force` (and so every variant build) compiles them all."""
     lib = out or LIB
-    if not force and not _stale(lib, DEPS):
+    headers = _headers()
+    if not force and not _stale(lib, SOURCES + headers):
         return lib
     objs = []
+    compiled = False
     tag = "" if out is None else "_" + os.path.basename(out).replace(".so", "")
     for src in SOURCES:
         obj = os.path.join(HERE, "csrc", "_obj" + tag, os.path.basename(src) + ".o")
+        objs.append(obj)
+        if not force and not _stale(obj, [src] + headers):
+            continue
         os.makedirs(os.path.dirname(obj), exist_ok=True)
         cmd = [HIPCC] + COMMON + list(extra)
         if src.endswith(".hip"):
@@ -75,11 +85,15 @@ def build_product(force=False, verbose=False, extra=(), out=None):
             # another directory would hash differently (grayshift_amd/codeobj.py keys the
             # committed PMC summaries by the code objects' hash).
             cmd += ["-cuid=gs_" + os.path.basename(src).replace(".", "_")]
+        # (the .cpp files are plain C++ over the HIP runtime API: a HIP translation unit, even
+        # one without kernels, would add a bundle to .hip_fatbin and change that hash)
         cmd += ["-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-        objs.append(obj)
+        compiled = True
+    if not compiled and not _stale(lib, objs):
+        return lib
     tmp = lib + ".tmp"
     cmd = [HIPCC, "-shared", "--offload-arch=" + ARCH, "-o", tmp] + objs + ["-lpthread", "-ldl"]
     if verbose:
@@ -95,7 +109,7 @@ KAT_LIB = os.path.join(ROOT, "tests", "hip", "libkat_device.so")
 
 def build_kat(force=False, verbose=False):
     """Test-only HIP harness running the kernel's device functions on test arrays."""
-    deps = [KAT_SRC] + DEPS
+    deps = [KAT_SRC] + _headers()
     if not force and not _stale(KAT_LIB, deps):
         return KAT_LIB
     cmd = [HIPCC] + COMMON + ["-x", "hip", "--offload-arch=" + ARCH, "-shared", "-o", KAT_LIB + ".tmp", KAT_SRC]

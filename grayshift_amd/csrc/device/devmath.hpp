@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernel_abi.hpp"
+
 namespace gsd {
 
 struct d3 {
@@ -72,23 +74,7 @@ __device__ __forceinline__ uint64_t stream_seed(uint64_t seed, uint32_t pixel, u
     return splitmix64(seed ^ splitmix64(((uint64_t)sample << 32) | (uint64_t)pixel));
 }
 
-// Unsigned 32-bit division by a divisor fixed for a launch (image width, tiles per row,
-// chunks per pixel, ...): the round-up multiply-shift method (Granlund & Montgomery
-// 1994; Hacker's Delight 10-8), exact for every n < 2^32 and every d >= 1 -- 5 VALU
-// instead of the ~18 of a division by a runtime value.  The host fills the magic.
-struct UDiv {
-    uint32_t d, m, s1, s2;
-};
-__host__ __device__ inline UDiv udiv_make(uint32_t d) {
-    uint32_t l = 0;
-    while (l < 32 && (1ull << l) < d) l++;  // ceil(log2 d)
-    UDiv u;
-    u.d = d;
-    u.m = (uint32_t)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-    u.s1 = l < 1 ? l : 1;
-    u.s2 = l < 1 ? 0 : l - 1;
-    return u;
-}
+// n / u.d by the multiply-shift form the host made (UDiv, udiv_make: kernel_abi.hpp)
 __device__ __forceinline__ uint32_t udiv(uint32_t n, const UDiv& u) {
     const uint32_t t = __umulhi(n, u.m);
     return (t + ((n - t) >> u.s1)) >> u.s2;

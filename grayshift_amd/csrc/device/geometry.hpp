@@ -1,20 +1,15 @@
 // geometry.hpp — device-side restatements of the reference's geometric tests
 // (AABB.rs, sphere.rs, quad.rs/plane.rs, triangle.rs, hittable.rs Translate/RotateY)
-// and the device records they read.  Shared by the megakernel (render.hip) and the
+// over the device records they read (DNode, DSphere, TNode, TLeaf, TBox, TQuad: kernel_abi.hpp,
+// which the host files share).  Shared by the megakernel (render.hip) and the
 // device known-answer-test harness (tests/hip/kat_device.hip).
 #pragma once
 #include "../../../include/grayshift_gpu.h"
+#include "kernel_abi.hpp"
 #include "devmath.hpp"
 
 namespace gsd {
 
-struct alignas(16) DNode {  // 64 B: box (f64, as AABB.rs) + children
-    double mnx, mny, mnz, mxx, mxy, mxz;
-    uint32_t left, right, pad0, pad1;
-};
-struct alignas(16) DSphere {  // 32 B: what Sphere::hit reads; material kept apart
-    double cx, cy, cz, r;
-};
 struct Ray {
     d3 o, d;
     double time;
@@ -175,27 +170,6 @@ __device__ __forceinline__ bool box_hit_fast(const DNode& n, const d3& o, const 
 // 3.01u (|hi'| + lo' + 2R): (1 - 3.01u)(lo' + |hi'|) > 15.8 u R > 6.02 u R.  Undecided is
 // then -thr' <= d <= thr'.
 #define GS_CERT_K 4.76837158203125e-07f  // 2^-21
-
-struct alignas(16) TNode {  // 32 B record of the threaded tree: f32 box (paired for box_cert) + hit / miss links
-    float mnx, mny, mxx, mxy, mnz, mxz;
-    uint32_t hit, miss;
-};
-struct alignas(16) TLeaf {  // 48 B leaf record: a stationary sphere inline, next link, ABI ref
-    // rr = radius * radius, Sphere::hit's `self.radius * self.radius` (sphere.rs:70) taken
-    // once on the host: the same IEEE product the test would take per ray (round 5)
-    double cx, cy, cz, rr;
-    uint32_t next, ref, pad0, pad1;
-};
-struct alignas(16) TBox {  // 48 B: the node's f64 box (AABB.rs), for undecided and non-cert rays
-    double mnx, mny, mnz, mxx, mxy, mxz;
-};
-// 128 B traversal copy of a quad (the ABI gs_quad, material aside), ordered by use: the
-// plane (normal, D: 32 B) decides most tests; Q, u, v, w (96 B) are read only for a plane
-// hit inside the interval.
-struct alignas(16) TQuad {
-    double nx, ny, nz, d;
-    double qx, qy, qz, ux, uy, uz, vx, vy, vz, wx, wy, wz;
-};
 
 typedef float gs_f2 __attribute__((ext_vector_type(2)));
 // Per-ray constants of the certified test, paired so that one packed FMA (v_pk_fma_f32:

@@ -1,0 +1,19 @@
+// kernels.hpp — what render.hip offers the host files (csrc/host/scene.cpp, launch.cpp): which
+// gs_render_kernel instantiations exist, and one launcher per kernel.  Kernel pointers feed
+// hipFuncGetAttributes and the occupancy query on the host side; only render.hip launches.
+#pragma once
+#include "kernel_abi.hpp"
+
+// The instantiation for a feature set (gs_render_kernel<0> when there is none for it).
+void (*kernel_for(int feat))(KArgs);
+// A split batch round may take the (feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT) instantiation.
+bool has_rsplit(int feat);
+
+// Each enqueues one kernel on `st` and returns that launch's error (hipGetLastError()).
+hipError_t launch_params_kernel(hipStream_t st, const KParams& kp, KParams* dst);  // (zeroes the queue)
+hipError_t launch_combine_kernel(hipStream_t st, unsigned grid, const KParams* P);
+hipError_t launch_round_init_kernel(hipStream_t st, unsigned grid, const KParams* P);
+hipError_t launch_round_params_kernel(hipStream_t st, KParams* P, uint32_t round, uint32_t seg, uint32_t seg_px,
+                                      int32_t chunk_req, int32_t whole_mode);
+hipError_t launch_round_combine_kernel(hipStream_t st, unsigned grid, const KParams* P, uint32_t round);
+hipError_t launch_render_kernel(hipStream_t st, void (*kernel)(KArgs), unsigned blocks, size_t lds, const KArgs& a);

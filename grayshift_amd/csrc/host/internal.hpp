@@ -1,4 +1,4 @@
-// internal.hpp — library-internal entry points shared by render.hip and the host files
+// internal.hpp — library-internal entry points shared by the host files (launch.cpp, multi_gpu.cpp)
 // (not part of the C-ABI in include/).
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -20,11 +20,11 @@ gs_status gs_render_tiles_timed_async(const gs_device_scene* ds, const gs_camera
 
 // The placement pilots still pending for a launch of `cam` / `ss` on n devices (scenes[i] on
 // devices[i], its stream streams[i]): every device's pilot is launched before any is waited
-// for, so the first frame of an N-GPU context pilots concurrently (render.hip).  *ran: whether
+// for, so the first frame of an N-GPU context pilots concurrently (launch.cpp).  *ran: whether
 // any pilot ran.  Leaves the current device changed.
 gs_status gs_placement_prepare(gs_device_scene* const* scenes, const int* devices, void* const* streams, int n,
                                const gs_camera* cam, const gs_sample_settings* ss, int* ran);
 
 // A timed frame of the scene on its device: its megakernel time and samples (paths), which
-// set the scene's per-sample cost that the guided tail's small-frame rule reads (render.hip).
+// set the scene's per-sample cost that the guided tail's small-frame rule reads (launch.cpp).
 extern "C" void gs_device_scene_note_frame(gs_device_scene* ds, double kernel_ms, uint64_t samples);

@@ -272,7 +272,7 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
     gs_status s = partition(cam, seed, &plan_ms);
     if (s != GS_OK) return s;
     {
-        // The scenes' placement pilots (first frame, render.hip run before the first launch):
+        // The scenes' placement pilots (first frame, launch.cpp, run before the first launch):
         // launched on every device before any is waited for, outside the timed render.
         std::vector<gs_device_scene*> sc(n);
         std::vector<void*> st(n);

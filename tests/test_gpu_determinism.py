@@ -2,7 +2,7 @@
 r5 item 2): not on the device count, the tile assignment, the rank's capacity, the guided
 tail's placement or a timing measured by an earlier frame.
 
-The chunk association (render.hip `launch`): a pixel's colour is the in-order sum of its
+The chunk association (launch.cpp `coarse_chunk`): a pixel's colour is the in-order sum of its
 chunks of c samples, c fixed by (W x H, spp, the scene's flags, the knobs).  The guided tail's
 1-sample items are regrouped into those chunks by gs_combine_kernel, so how many tiles of a
 rank run in the tail -- which depends on the rank's capacity, the device's lanes and, for small

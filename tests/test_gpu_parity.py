@@ -304,7 +304,7 @@ def test_full_size_frames(name, spp):
 @pytest.mark.parametrize("name,width,cpp", [("C3", 64, None), ("C5", 64, None), ("C5", 64, 16), ("C5", 48, 8)])
 def test_stated_spp_configs_vs_oracle(name, width, cpp):
     """C3 at its full 1024 spp and C5 at its full 4096 spp (reduced width), rendered
-    through the auto sample-chunk rule (render.hip: 16-sample chunks, or batch/64, then
+    through the auto sample-chunk rule (launch.cpp coarse_chunk: 16-sample chunks, or batch/64, then
     doubled while the chunk sums exceed the budget).  C3 at 1024 spp: 64 chunks of 16
     per pixel.  C5 at 3840x2160 takes the doubling branch (4096 spp: 256-sample chunks,
     16 per pixel); a test budget of capacity x cpp x 24 bytes makes this small frame
@@ -328,7 +328,7 @@ def test_stated_spp_configs_vs_oracle(name, width, cpp):
 def test_guided_tail_settings_vs_oracle(chunk, fine, pct):
     """C1's scene at 100 spp, 160x90 (six 64x64 tile slots) under other guided-tail settings:
     tails of 1 or 2 tiles (coarse and fine chunk sums both present: the chunk-major layout's
-    two regions, render.hip KParams.partial), an explicit 8-sample coarse chunk with a tail,
+    two regions, kernel_abi.hpp KParams.partial), an explicit 8-sample coarse chunk with a tail,
     and the default and a 4x tail (every tile in 1-sample items) -- against the oracle,
     counters exact.  The tail is scheduling only (round 6): its 1-sample sums are regrouped
     into the coarse chunks, so the frame equals the same coarse chunking without a tail bit for

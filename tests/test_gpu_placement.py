@@ -1,5 +1,5 @@
-"""Placement of the threaded BVH records in the per-block LDS mirror (render.hip
-place_records / run_pilot): the first launch of a scene whose records do not all fit
+"""Placement of the threaded BVH records in the per-block LDS mirror (scene.cpp
+place_records, launch.cpp pilot_begin / pilot_end): the first launch of a scene whose records do not all fit
 runs a pilot that counts every record's tests and re-places the records by measured
 visits per byte.  Placement must never change a frame or a counter, the pilot's counts
 must be the frame's own work counts, and the re-placed mirror must serve more of the
