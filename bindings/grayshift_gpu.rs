@@ -133,6 +133,13 @@ pub struct gs_stats {
 /// The persistent N-GPU frame context (ABI 6, opaque).
 #[repr(C)] pub struct gs_multi { _private: [u8; 0] }
 
+/// An open accumulation of the frame context (progressive rendering; additive, ABI 11).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_accum_info {
+    pub width: i32, pub height: i32, pub chunk: u32, pub passes: u32, pub seed: u64, pub samples: u64,
+    pub last_delta: f64, pub counters: gs_counters,
+}
+
 /// What gs_device_scene_create built (ABI 5).
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct gs_scene_info {
@@ -214,6 +221,20 @@ extern "C" {
     pub fn gs_multi_destroy(m: *mut gs_multi) -> gs_status;
     pub fn gs_debug_set_multi_collective(always: i32) -> gs_status;
     pub fn gs_debug_set_multi_same_device(on: i32) -> gs_status;
+    /// Progressive rendering: passes over device-resident f64 sums.  Passes of n_1, n_2, ...
+    /// samples leave the bits of one render of their total (same seed and chunk).
+    pub fn gs_render_tiles_pass_async(scene: *const gs_device_scene, cam: *const gs_camera, samples: u32, seed: u64,
+                                      part: *const gs_partition, sample_base: u32, chunk: u32, d_sums: *mut f64,
+                                      out: *const gs_render_outputs, d_counters: *mut gs_counters,
+                                      stream: *mut c_void) -> gs_status;
+    pub fn gs_multi_accum_begin(m: *mut gs_multi, cam: *const gs_camera, seed: u64, chunk: u32) -> gs_status;
+    pub fn gs_multi_accum_pass(m: *mut gs_multi, samples: u32, out: *const gs_multi_outputs,
+                               stats: *mut gs_stats) -> gs_status;
+    pub fn gs_multi_accum_info(m: *const gs_multi, info: *mut gs_accum_info) -> gs_status;
+    pub fn gs_multi_accum_download(m: *mut gs_multi, sums: *mut f64) -> gs_status;
+    pub fn gs_multi_accum_upload(m: *mut gs_multi, cam: *const gs_camera, seed: u64, chunk: u32, samples: u64,
+                                 sums: *const f64, counters: *const gs_counters) -> gs_status;
+    pub fn gs_multi_accum_end(m: *mut gs_multi) -> gs_status;
 }
 
 pub fn last_error() -> String {

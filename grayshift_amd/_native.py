@@ -152,6 +152,17 @@ class gs_scene_info(C.Structure):
                 ("placement", C.c_int32), ("long_samples", C.c_int32), ("pilot_ms", C.c_double)]
 
 
+class gs_accum_info(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("chunk", C.c_uint32), ("passes", C.c_uint32),
+                ("seed", C.c_uint64), ("samples", C.c_uint64), ("last_delta", C.c_double),
+                ("counters", gs_counters)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "counters"}
+        d["counters"] = self.counters.as_dict()
+        return d
+
+
 # Every symbol include/*.h declares, with its ctypes signature.
 _P = C.c_void_p
 SIGNATURES = {
@@ -210,6 +221,16 @@ SIGNATURES = {
     "gs_multi_destroy": (C.c_int32, [_P]),
     "gs_debug_set_multi_collective": (C.c_int32, [C.c_int32]),
     "gs_debug_set_multi_same_device": (C.c_int32, [C.c_int32]),
+    "gs_render_tiles_pass_async": (C.c_int32, [_P, C.POINTER(gs_camera), C.c_uint32, C.c_uint64,
+                                               C.POINTER(gs_partition), C.c_uint32, C.c_uint32, _P,
+                                               C.POINTER(gs_render_outputs), _P, _P]),
+    "gs_multi_accum_begin": (C.c_int32, [_P, C.POINTER(gs_camera), C.c_uint64, C.c_uint32]),
+    "gs_multi_accum_pass": (C.c_int32, [_P, C.c_uint32, C.POINTER(gs_multi_outputs), C.POINTER(gs_stats)]),
+    "gs_multi_accum_info": (C.c_int32, [_P, C.POINTER(gs_accum_info)]),
+    "gs_multi_accum_download": (C.c_int32, [_P, _P]),
+    "gs_multi_accum_upload": (C.c_int32, [_P, C.POINTER(gs_camera), C.c_uint64, C.c_uint32, C.c_uint64, _P,
+                                          C.POINTER(gs_counters)]),
+    "gs_multi_accum_end": (C.c_int32, [_P]),
     # grayshift_host.h
     "gs_host_scene_from_spec": (C.c_int32, [C.POINTER(gs_scene_spec), C.POINTER(_P)]),
     "gs_host_scene_destroy": (C.c_int32, [_P]),

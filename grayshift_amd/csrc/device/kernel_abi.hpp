@@ -266,7 +266,24 @@ struct KParams {
     // walks a BVH under an instance chain: o, d (6 doubles), the return link (u32), and (the
     // general kernel) a hit's outer chain -- slot k of lane g at [k * grid lanes + g]
     double* nest_save;
+    // Progressive passes (gs_render_tiles_pass_async; DESIGN.md §3.2 "Progressive passes"):
+    // this launch renders samples [sample_base, sample_base + ss.batch_size) of every pixel,
+    // and gs_accumulate_kernel takes gs_combine_kernel's place: it adds the pass's chunk sums
+    // to accum (capacity * 3 f64, packed order) and resolves accum / (sample_base + batch_size).
+    // Every other launch has sample_base 0 and accum null.
+    uint32_t sample_base, pad2;
+    double* accum;
+    // [gs_accum_blocks(capacity)] per-block sums of |colour after - colour before| (nullable)
+    double* delta;
 };
+
+// gs_accumulate_kernel's grid: one block of 256 per 256 packed pixels up to 2048 blocks (a
+// grid-stride loop past that) -- a function of the capacity alone, so the per-block partial
+// sums of the pass's change, and their sum in index order, do not depend on the device.
+#define GS_ACCUM_MAX_BLOCKS 2048u
+__host__ __device__ constexpr uint32_t gs_accum_blocks(uint32_t capacity) {
+    return capacity == 0u ? 1u : ((capacity - 1u) / 256u + 1u < GS_ACCUM_MAX_BLOCKS ? (capacity - 1u) / 256u + 1u : GS_ACCUM_MAX_BLOCKS);
+}
 
 // Hot kernel arguments: what the traversal loop reads every step.
 struct KArgs {

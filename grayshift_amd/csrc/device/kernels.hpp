@@ -12,6 +12,8 @@ bool has_rsplit(int feat);
 // Each enqueues one kernel on `st` and returns that launch's error (hipGetLastError()).
 hipError_t launch_params_kernel(hipStream_t st, const KParams& kp, KParams* dst);  // (zeroes the queue)
 hipError_t launch_combine_kernel(hipStream_t st, unsigned grid, const KParams* P);
+// (a progressive pass's combine; its grid is gs_accum_blocks(capacity), the size of KParams::delta)
+hipError_t launch_accumulate_kernel(hipStream_t st, const KParams* P, uint32_t capacity);
 hipError_t launch_round_init_kernel(hipStream_t st, unsigned grid, const KParams* P);
 hipError_t launch_round_params_kernel(hipStream_t st, KParams* P, uint32_t round, uint32_t seg, uint32_t seg_px,
                                       int32_t chunk_req, int32_t whole_mode);

@@ -1583,7 +1583,7 @@ __global__ __launch_bounds__(GS_BLOCK, GS_MIN_WAVES) void gs_render_kernel(KArgs
                             // queue position share a tile, so both are in the fine region or neither)
                             LI(L_ITEM) = fine ? P->fine_base + ck * (P->capacity - P->fine_px) + (item - P->fine_px)
                                               : ck * P->fine_px + item;
-                            LI(L_SAMPLE) = ck * csz;
+                            LI(L_SAMPLE) = P->sample_base + ck * csz;  // (sample_base: a progressive pass's first sample, else 0)
                             LI(L_BLEFT) = min(csz, P->ss.batch_size - ck * csz);
                             if (ck == 0) atomicAdd(&s_cnt[C_PIX], 1ull);
                         } else if (P->rounds) {
@@ -2353,6 +2353,99 @@ __global__ void gs_combine_kernel(const KParams* __restrict__ P) {
     }
 }
 
+// Progressive passes: gs_combine_kernel for a launch that continues a frame.  The pass rendered
+// samples [sample_base, sample_base + batch_size) of every pixel; a pixel's running sums
+// (accum, f64, packed order) take the pass's chunk sums in chunk order -- the combine's own
+// additions, the tail's 1-sample sums re-formed into chunks of P->chunk first -- so after K
+// passes of n samples they hold ((0 + C_0) + C_1) + ... over all K n / c chunks: a one-shot
+// K n-spp render's sums, bit for bit, and sums / (K n) is its colour.
+// The pass's change, Σ over real pixels and channels of |colour after - colour before| (the
+// f64 colours; before = 0 for the first pass): each thread adds its pixels' terms in pixel
+// order, the block folds its 256 values through LDS in a fixed tree, and block b's sum goes
+// to delta[b] -- no float atomics, and the grid is gs_accum_blocks(capacity), so the values
+// depend on the capacity alone.  The host adds the partials in index order.
+__global__ __launch_bounds__(256) void gs_accumulate_kernel(const KParams* __restrict__ P) {
+    __shared__ double s_red[256];
+    const uint32_t cpp = P->cpp;
+    const uint32_t base = P->sample_base, bs = P->ss.batch_size;
+    const double n_before = (double)base, n_after = (double)(base + bs);
+    double change = 0.0;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < P->capacity; k += gridDim.x * blockDim.x) {
+        uint32_t pi = 0, pj = 0;
+        const bool real = packed_pixel(P, k, pi, pj);
+        const size_t oi = P->direct ? (size_t)pj * (uint32_t)P->cam.image_width + pi : (size_t)k;
+        float* o = P->out ? P->out + oi * 3 : nullptr;
+        uint8_t* o8 = P->out8 ? P->out8 + oi * 3 : nullptr;
+        if (!real) {
+            if (P->direct) continue;
+            if (o) {
+                o[0] = 0.0f;
+                o[1] = 0.0f;
+                o[2] = 0.0f;
+            }
+            if (o8) {
+                o8[0] = 0;
+                o8[1] = 0;
+                o8[2] = 0;
+            }
+            continue;
+        }
+        const bool fine = k >= P->fine_px;
+        // chunk-major sums: consecutive lanes read consecutive 24-B sums of each chunk
+        const size_t stride = (size_t)(fine ? P->capacity - P->fine_px : P->fine_px) * 3;
+        const double* p = P->partial + (fine ? (size_t)P->fine_base + (k - P->fine_px) : (size_t)k) * 3;
+        double* acc = P->accum + (size_t)k * 3;
+        const double r0 = acc[0], g0 = acc[1], b0 = acc[2];
+        double r = r0, g = g0, b = b0;
+        if (!fine) {
+            for (uint32_t c = 0; c < cpp; c++, p += stride) {
+                r += p[0];
+                g += p[1];
+                b += p[2];
+            }
+        } else {
+            const uint32_t c = P->chunk;  // (bs is a multiple of c: gs_render_tiles_pass_async)
+            for (uint32_t s0 = 0; s0 < bs; s0 += c) {
+                const uint32_t e = min(bs, s0 + c);
+                double cr = 0.0, cg = 0.0, cb = 0.0;
+                for (uint32_t s = s0; s < e; s++, p += stride) {
+                    cr += p[0];
+                    cg += p[1];
+                    cb += p[2];
+                }
+                r += cr;
+                g += cg;
+                b += cb;
+            }
+        }
+        acc[0] = r;
+        acc[1] = g;
+        acc[2] = b;
+        const double cr = r / n_after, cg = g / n_after, cb = b / n_after;
+        if (o) {
+            o[0] = (float)cr;
+            o[1] = (float)cg;
+            o[2] = (float)cb;
+        }
+        if (o8) {
+            o8[0] = color_byte(cr);
+            o8[1] = color_byte(cg);
+            o8[2] = color_byte(cb);
+        }
+        const double pr = base ? r0 / n_before : 0.0, pg = base ? g0 / n_before : 0.0, pb = base ? b0 / n_before : 0.0;
+        change += fabs(cr - pr);
+        change += fabs(cg - pg);
+        change += fabs(cb - pb);
+    }
+    s_red[threadIdx.x] = change;
+    __syncthreads();
+    for (uint32_t h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) s_red[threadIdx.x] += s_red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && P->delta) P->delta[blockIdx.x] = s_red[0];
+}
+
 // ------------------------------------------------ adaptive sampling in batch rounds
 // The reference's adaptive loop (camera.rs:135-165) runs a pixel's batches one after the
 // other, each batch's stop test over the running sums.  Per-lane that puts up to
@@ -2615,6 +2708,10 @@ hipError_t launch_params_kernel(hipStream_t st, const KParams& kp, KParams* dst)
 }
 hipError_t launch_combine_kernel(hipStream_t st, unsigned grid, const KParams* P) {
     hipLaunchKernelGGL(gs_combine_kernel, dim3(grid), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+hipError_t launch_accumulate_kernel(hipStream_t st, const KParams* P, uint32_t capacity) {
+    hipLaunchKernelGGL(gs_accumulate_kernel, dim3(gs_accum_blocks(capacity)), dim3(256), 0, st, P);
     return hipGetLastError();
 }
 hipError_t launch_round_init_kernel(hipStream_t st, unsigned grid, const KParams* P) {

@@ -18,6 +18,17 @@ gs_status gs_render_tiles_timed_async(const gs_device_scene* ds, const gs_camera
                                       gs_counters* d_counters, void* stream, hipEvent_t k_begin, hipEvent_t k_end,
                                       bool direct = false, bool zero_counters = false);
 
+// gs_render_tiles_pass_async with the same extras, and the pass's change: d_delta (nullable)
+// receives gs_pass_delta_blocks(capacity) per-block sums of |colour after - colour before| over
+// this rank's real pixels and channels (f64 colours; before = 0 when sample_base is 0), to be
+// added in index order.  The block count depends on the capacity alone.
+gs_status gs_render_tiles_pass_timed_async(const gs_device_scene* ds, const gs_camera* cam, uint32_t samples,
+                                           uint64_t seed, const gs_partition* part, uint32_t sample_base,
+                                           uint32_t chunk, double* d_sums, double* d_delta,
+                                           const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
+                                           hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters);
+int64_t gs_pass_delta_blocks(int64_t capacity);
+
 // The placement pilots still pending for a launch of `cam` / `ss` on n devices (scenes[i] on
 // devices[i], its stream streams[i]): every device's pilot is launched before any is waited
 // for, so the first frame of an N-GPU context pilots concurrently (launch.cpp).  *ran: whether

@@ -211,10 +211,17 @@ struct VisitArgs {
     uint32_t* visits;
     uint32_t leaf_base;
 };
+// A progressive pass (gs_render_tiles_pass_async): the launch renders samples [sample_base,
+// sample_base + ss->batch_size) in chunks of `chunk`, and gs_accumulate_kernel adds them to d_sums.
+struct PassArgs {
+    uint32_t sample_base, chunk;
+    double* d_sums;
+    double* d_delta;  // [gs_accum_blocks(capacity)], nullable
+};
 static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                         const gs_partition* part, const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
                         hipEvent_t k_begin, hipEvent_t k_end, const VisitArgs* va, bool direct = false,
-                        bool zero_counters = false);
+                        bool zero_counters = false, const PassArgs* pass = nullptr);
 static gs_status ensure_placement(gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss,
                                   void* stream);
 
@@ -226,6 +233,50 @@ gs_status gs_render_tiles_timed_async(const gs_device_scene* ds, const gs_camera
     gs_status e = ensure_placement(const_cast<gs_device_scene*>(ds), cam, ss, stream);
     if (e != GS_OK) return e;
     return launch(ds, cam, ss, seed, part, outs, d_counters, stream, k_begin, k_end, nullptr, direct, zero_counters);
+}
+
+// The checks of a progressive pass, all on the arguments alone: nothing here reads the scene or
+// touches a device.
+static gs_status check_pass(const gs_device_scene* ds, const gs_camera* cam, uint32_t samples, const gs_partition* part,
+                            uint32_t sample_base, uint32_t c, const double* d_sums, const gs_render_outputs* outs) {
+    if (!ds || !cam || !part || !d_sums || !outs || (!outs->rgb && !outs->rgb8)) return fail(GS_ERR_ARG, "null argument");
+    if (samples == 0) return fail(GS_ERR_ARG, "a pass of 0 samples");
+    if (samples % c != 0) return fail(GS_ERR_ARG, "samples is not a multiple of the chunk");
+    if (sample_base % c != 0) return fail(GS_ERR_ARG, "sample_base is not a multiple of the chunk");
+    if (samples / c > 64u) return fail(GS_ERR_ARG, "more than 64 chunks in one pass");
+    if ((uint64_t)sample_base + samples > 0xFFFFFFFFull) return fail(GS_ERR_ARG, "sample_base + samples overflows 32 bits");
+    const int64_t cap = gs_partition_capacity(cam, part);
+    if (cap < 0) return fail(GS_ERR_ARG, "bad partition / image size");
+    if ((uint64_t)cap * (samples / c) * 24u > read_knobs().partial_budget)
+        return fail(GS_ERR_ARG, "the pass's chunk sums exceed the partial budget: fewer samples per pass");
+    return GS_OK;
+}
+
+gs_status gs_render_tiles_pass_timed_async(const gs_device_scene* ds, const gs_camera* cam, uint32_t samples,
+                                           uint64_t seed, const gs_partition* part, uint32_t sample_base,
+                                           uint32_t chunk, double* d_sums, double* d_delta,
+                                           const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
+                                           hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters) {
+    const uint32_t c = chunk ? chunk : 16u;
+    gs_status e = check_pass(ds, cam, samples, part, sample_base, c, d_sums, outs);
+    if (e != GS_OK) return e;
+    const gs_sample_settings ss{0.0, 0.0, samples, 0};  // one batch of `samples` (max_samples < batch_size)
+    e = ensure_placement(const_cast<gs_device_scene*>(ds), cam, &ss, stream);
+    if (e != GS_OK) return e;
+    const PassArgs pa{sample_base, c, d_sums, d_delta};
+    return launch(ds, cam, &ss, seed, part, outs, d_counters, stream, k_begin, k_end, nullptr, direct, zero_counters, &pa);
+}
+
+extern "C" gs_status gs_render_tiles_pass_async(const gs_device_scene* ds, const gs_camera* cam, uint32_t samples,
+                                                uint64_t seed, const gs_partition* part, uint32_t sample_base,
+                                                uint32_t chunk, double* d_sums, const gs_render_outputs* outs,
+                                                gs_counters* d_counters, void* stream) {
+    return gs_render_tiles_pass_timed_async(ds, cam, samples, seed, part, sample_base, chunk, d_sums, nullptr, outs,
+                                            d_counters, stream, nullptr, nullptr, false, false);
+}
+
+int64_t gs_pass_delta_blocks(int64_t capacity) {
+    return capacity <= 0 || capacity >= 0xFFFFFFFFll ? 1 : (int64_t)gs_accum_blocks((uint32_t)capacity);
 }
 
 // ---------------------------------------------------------------- the work plan
@@ -350,6 +401,26 @@ static WorkPlan plan_work(const gs_camera& cam, const gs_sample_settings& ss, co
             w.fine_px = cap, w.fine_chunk = 1, w.fine_cpp = 1;
         }
     }
+    return w;
+}
+
+// The plan for a progressive pass: always chunked, the coarse chunk `c` as the caller gave it
+// (coarse_chunk's frame- and size-dependent rules do not apply: every pass of the frame must
+// cut its samples the same way).  The guided tail, being scheduling only, is sized as usual;
+// a small frame of a simple scene takes none while its samples are short (coarse_chunk's
+// small-frame rule, here deciding the tail alone).
+static WorkPlan plan_pass(const gs_camera& cam, uint32_t bs, const gs_partition& part, uint32_t cap, uint32_t c,
+                          int feat, const Knobs& k, uint64_t lanes, bool long_samples) {
+    WorkPlan w;
+    w.fine_px = cap;
+    w.chunk = c;
+    w.cpp = bs / c;
+    const uint64_t frame_px = (uint64_t)cam.image_width * (uint64_t)cam.image_height;
+    const bool simple = (feat & (GS_FEAT_MEDIA | GS_FEAT_NESTED | GS_FEAT_MIXED)) == 0;
+    const bool small = k.tail_pct == 0 && simple && frame_px * bs <= 4ull * (256ull * GS_BLOCK) * c;
+    guided_tail(CoarseChunk{c, small}, bs, cap, (uint64_t)part.tile_w * part.tile_h, lanes, long_samples, k, w);
+    if ((uint64_t)w.fine_px * w.cpp + ((uint64_t)cap - w.fine_px) * w.fine_cpp >= 0xFFFFFFFFull)
+        w.fine_px = cap, w.fine_chunk = 1, w.fine_cpp = 1;
     return w;
 }
 
@@ -599,7 +670,7 @@ static gs_status enqueue_rounds(const Enqueue& q, const WorkPlan& w, const Knobs
 
 // One megakernel launch, then the chunk combine when the pixels' samples were split.
 static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const LaunchReq& r, const KParams* dP,
-                               const KArgs& a) {
+                               const KArgs& a, bool pass) {
     if (q.k_begin) HIPCHK(hipEventRecord(q.k_begin, q.st));
     const bool pilot_kernel = r.va != nullptr;
     // (a fixed-spp chunked launch takes the instantiation without the adaptive paths)
@@ -607,7 +678,9 @@ static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const Launch
     HIPCHK(launch_render_kernel(q.st, kernel_for(pilot_kernel ? GS_FEAT_PILOT : q.feat | (fixed ? GS_FEAT_FIXED : 0)),
                                 q.blocks, q.lds, a));
     if (q.k_end) HIPCHK(hipEventRecord(q.k_end, q.st));
-    if (w.chunk) {
+    if (pass) {  // (always chunked: the pass's sums join the frame's)
+        HIPCHK(launch_accumulate_kernel(q.st, dP, r.cap));
+    } else if (w.chunk) {
         const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)r.cap + 255) / 256, 8192);
         HIPCHK(launch_combine_kernel(q.st, grid, dP));
     }
@@ -619,7 +692,8 @@ static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const Launch
 // dominant kernel alone (csrc/host/internal.hpp; the frame context's gs_stats.kernel_ms).
 static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                         const gs_partition* part, const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
-                        hipEvent_t k_begin, hipEvent_t k_end, const VisitArgs* va, bool direct, bool zero_counters) {
+                        hipEvent_t k_begin, hipEvent_t k_end, const VisitArgs* va, bool direct, bool zero_counters,
+                        const PassArgs* pass) {
     if (!ds || !cam || !ss || !part || !outs || (!outs->rgb && !outs->rgb8)) return fail(GS_ERR_ARG, "null argument");
     if (!part_ok(cam, part)) return fail(GS_ERR_ARG, "bad partition / image size");
     if (ss->batch_size == 0) return fail(GS_ERR_ARG, "batch_size 0 never terminates (camera.rs:137)");
@@ -645,8 +719,9 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     const bool visit_out = outs->item_visits != nullptr;
 #endif
     const uint64_t lanes = (uint64_t)std::max(1, device_cus(dev)) * GS_BLOCK;
-    const WorkPlan w = plan_work(*cam, *ss, *part, req.cap, ds->feat, k, lanes,
-                                 ds->long_samples.load(std::memory_order_relaxed), !visit_out && !va);
+    const bool long_samples = ds->long_samples.load(std::memory_order_relaxed);
+    const WorkPlan w = pass ? plan_pass(*cam, ss->batch_size, *part, req.cap, pass->chunk, ds->feat, k, lanes, long_samples)
+                            : plan_work(*cam, *ss, *part, req.cap, ds->feat, k, lanes, long_samples, !visit_out && !va);
     // (under the scene's mutex from here: the placement pilot's end rewrites the records,
     // the root and the mirror prefixes under it, pilot_end)
     gs_device_scene* mds = const_cast<gs_device_scene*>(ds);
@@ -665,6 +740,11 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     if (blocks > max_blocks) blocks = max_blocks;
     if (blocks < 1) blocks = 1;
     KParams kp = fill_params(ds, req, w, blocks);
+    if (pass) {
+        kp.sample_base = pass->sample_base;
+        kp.accum = pass->d_sums;
+        kp.delta = pass->d_delta;
+    }
     // The u32 queue counter runs past n_items by at most one claim per wave (each wave's
     // last, failed claim): it must not wrap.
     if ((uint64_t)std::max<uint64_t>(kp.n_items, (uint64_t)w.seg_px * ss->batch_size) +
@@ -682,7 +762,7 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     if (outs->item_visits) HIPCHK(hipMemsetAsync(outs->item_visits, 0, (size_t)cap * sizeof(uint32_t), st));
     HIPCHK(launch_params_kernel(st, kp, sl.params));  // (zeroes the queue)
     const Enqueue q{st, (unsigned)blocks, lc.lds, lc.feat, k_begin, k_end};
-    e = w.n_rounds ? enqueue_rounds(q, w, k, req, kp, sl.params, a) : enqueue_frame(q, w, req, sl.params, a);
+    e = w.n_rounds ? enqueue_rounds(q, w, k, req, kp, sl.params, a) : enqueue_frame(q, w, req, sl.params, a, pass != nullptr);
     if (e != GS_OK) return e;
     HIPCHK(hipEventRecord(sl.done, st));
     sl.used = true;

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <mutex>
@@ -130,6 +131,10 @@ struct Device {
     // render start / end, megakernel start / end, gather + unpack start / end
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     DBuf order, packed, packed8, cnt;
+    // an open accumulation (gs_multi_accum_*): the rank's running sums (cap * 3 f64, packed
+    // order) and the last pass's per-block change, with its pinned host copy
+    DBuf sums, delta;
+    double* h_delta = nullptr;
     // the frame's counters, copied back on the stream behind the frame's last work, so the
     // host's wait is the only synchronisation (a synchronous copy after it cost C1 ~25 us)
     gs_counters* h_cnt = nullptr;  // pinned
@@ -179,6 +184,15 @@ struct gs_multi {
     DBuf gathered, gathered8, frame, frame8, text, scratch, len;
     bool have_rgb = false, have_rgb8 = false;
     int32_t frame_w = 0, frame_h = 0;
+    // The open accumulation (gs_multi_accum_begin .. _end): camera, seed and chunk are fixed,
+    // the tile plan is the one computed at its start, and acc_samples samples of every pixel
+    // are in the ranks' sums.
+    bool acc_open = false;
+    gs_camera acc_cam{};
+    uint64_t acc_seed = 0, acc_samples = 0;
+    uint32_t acc_chunk = 0, acc_passes = 0;
+    double acc_last_delta = 0.0;
+    gs_counters acc_counters{};
 
     ~gs_multi() {
         DeviceGuard g;
@@ -198,6 +212,9 @@ struct gs_multi {
             d.packed.release();
             d.packed8.release();
             d.cnt.release();
+            d.sums.release();
+            d.delta.release();
+            if (d.h_delta) (void)hipHostFree(d.h_delta);
             if (d.h_cnt) (void)hipHostFree(d.h_cnt);
             if (d.scene) gs_device_scene_destroy(d.scene);
             if (d.stream) (void)hipStreamDestroy(d.stream);
@@ -220,8 +237,16 @@ struct gs_multi {
     }
 
     gs_status partition(const gs_camera* cam, uint64_t seed, double* plan_ms);
+    // pass_samples != 0: a pass of the open accumulation (cam, ss and seed are then its own)
     gs_status render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, const gs_multi_outputs* out,
-                     gs_stats* stats);
+                     gs_stats* stats, uint32_t pass_samples = 0);
+    gs_status accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk);
+    void accum_end();
+    // The tile (or -1) of rank `rank`'s slot `slot`, and the slots the rank holds.
+    int64_t rank_slots(int rank) const;
+    int32_t slot_tile(int rank, int64_t slot) const;
+    // Moves the sums between the ranks' packed buffers and an [H][W][3] image (to_image or back).
+    gs_status permute_sums(double* image, bool to_image);
 };
 
 gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_ms) {
@@ -256,15 +281,16 @@ gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_
 }
 
 gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
-                           const gs_multi_outputs* out, gs_stats* stats) {
+                           const gs_multi_outputs* out, gs_stats* stats, uint32_t pass_samples) {
     if (!cam || !ss) return fail(GS_ERR_ARG, "null argument");
     if (out && !out->rgb && !out->rgb8 && !out->ppm_text) return fail(GS_ERR_ARG, "no output requested");
     if (out && out->ppm_text && !out->ppm_len) return fail(GS_ERR_ARG, "ppm_text without ppm_len");
     if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
     if (out && out->ppm_text && out->ppm_capacity < gs_ppm_max_bytes(cam->image_width, cam->image_height))
         return fail(GS_ERR_ARG, "ppm_capacity below gs_ppm_max_bytes");
-    std::lock_guard<std::mutex> lock(mu);
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
+    if (acc_open && !pass_samples)  // (a new plan would invalidate the packed sums)
+        return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
     DeviceGuard guard;
     const auto t0 = std::chrono::steady_clock::now();
     const int n = (int)dev.size();
@@ -307,8 +333,15 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         gs_render_outputs o{want_rgb ? (float*)(direct ? frame.p : d.packed.p) : nullptr,
                             want8 ? (uint8_t*)(direct ? frame8.p : d.packed8.p) : nullptr, nullptr};
         HIPOK(hipEventRecord(d.ev[0], d.stream));
-        s = gs_render_tiles_timed_async(d.scene, cam, ss, seed, &p, &o, (gs_counters*)d.cnt.p, d.stream, d.ev[2],
-                                        d.ev[3], direct, true);
+        if (pass_samples) {
+            HIPOK(hipMemsetAsync(d.delta.p, 0, (size_t)gs_pass_delta_blocks(cap) * 8, d.stream));
+            s = gs_render_tiles_pass_timed_async(d.scene, cam, pass_samples, seed, &p, (uint32_t)acc_samples, acc_chunk,
+                                                 (double*)d.sums.p, (double*)d.delta.p, &o, (gs_counters*)d.cnt.p,
+                                                 d.stream, d.ev[2], d.ev[3], direct, true);
+        } else {
+            s = gs_render_tiles_timed_async(d.scene, cam, ss, seed, &p, &o, (gs_counters*)d.cnt.p, d.stream, d.ev[2],
+                                            d.ev[3], direct, true);
+        }
         if (s != GS_OK) return s;
         HIPOK(hipEventRecord(d.ev[1], d.stream));
     }
@@ -390,6 +423,9 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
     for (auto& d : dev) {
         HIPOK(hipSetDevice(d.id));
         HIPOK(hipMemcpyAsync(d.h_cnt, d.cnt.p, sizeof(gs_counters), hipMemcpyDeviceToHost, d.stream));
+        if (pass_samples)
+            HIPOK(hipMemcpyAsync(d.h_delta, d.delta.p, (size_t)gs_pass_delta_blocks(cap) * 8, hipMemcpyDeviceToHost,
+                                 d.stream));
     }
     // Wait, then results.
     gs_counters total{};
@@ -424,6 +460,19 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         HIPOK(hipMemcpy(out->ppm_text, text.p, (size_t)l, hipMemcpyDeviceToHost));
         *out->ppm_len = l;
     }
+    if (pass_samples) {
+        // the pass's change: every rank's per-block partials in index order, the ranks in rank order
+        double change = 0.0;
+        const int64_t nb = gs_pass_delta_blocks(cap);
+        for (int i = 0; i < n; i++)
+            for (int64_t b = 0; b < nb; b++) change += dev[i].h_delta[b];
+        acc_last_delta = change / ((double)W * (double)H * 3.0);
+        gs_counters add = total;
+        if (acc_samples != 0) add.pixels = 0;  // (the kernel counts a pixel at chunk 0 of every pass)
+        add_counters(acc_counters, add);
+        acc_samples += pass_samples;
+        acc_passes += 1;
+    }
     const auto t1 = std::chrono::steady_clock::now();
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
@@ -443,7 +492,167 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
     return GS_OK;
 }
 
+// ---------------------------------------------------------------- progressive accumulation
+int64_t gs_multi::rank_slots(int rank) const {
+    if (!order.empty()) return slots;
+    gs_partition p{rank, (int32_t)dev.size(), tw, th, nullptr, 0, 0};
+    return gs_partition_capacity(&acc_cam, &p) / ((int64_t)tw * th);
+}
+
+int32_t gs_multi::slot_tile(int rank, int64_t slot) const {
+    const int64_t pos = rank + slot * (int64_t)dev.size();
+    return order.empty() ? (int32_t)pos : order[(size_t)pos];
+}
+
+gs_status gs_multi::accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk) {
+    if (acc_open) return fail(GS_ERR_ARG, "an accumulation is already open: gs_multi_accum_end first");
+    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
+    if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
+    DeviceGuard guard;
+    double plan_ms = 0.0;
+    gs_status s = partition(cam, seed, &plan_ms);
+    if (s != GS_OK) return s;
+    if (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll) return fail(GS_ERR_ARG, "bad partition");
+    const size_t nb = (size_t)gs_pass_delta_blocks(cap);
+    for (auto& d : dev) {
+        HIPOK(hipSetDevice(d.id));
+        GROW(d.sums, cap * 24);
+        GROW(d.delta, nb * 8);
+        HIPOK(hipMemsetAsync(d.sums.p, 0, (size_t)cap * 24, d.stream));
+        if (d.h_delta) (void)hipHostFree(d.h_delta);
+        d.h_delta = nullptr;
+        if (hipHostMalloc((void**)&d.h_delta, nb * 8, hipHostMallocDefault) != hipSuccess)
+            return fail(GS_ERR_OOM, "hipHostMalloc of the pass's change failed");
+        HIPOK(hipStreamSynchronize(d.stream));
+    }
+    acc_cam = *cam;
+    acc_seed = seed;
+    acc_chunk = chunk ? chunk : 16u;
+    acc_samples = 0;
+    acc_passes = 0;
+    acc_last_delta = 0.0;
+    acc_counters = gs_counters{};
+    acc_open = true;
+    return GS_OK;
+}
+
+void gs_multi::accum_end() {
+    DeviceGuard guard;
+    for (auto& d : dev) {
+        (void)hipSetDevice(d.id);
+        if (d.stream && !comms_broken) (void)hipStreamSynchronize(d.stream);
+        d.sums.release();
+        d.delta.release();
+        if (d.h_delta) (void)hipHostFree(d.h_delta);
+        d.h_delta = nullptr;
+    }
+    acc_open = false;
+}
+
+// Checkpoints are not hot: each rank's packed sums cross to the host whole, and the tile
+// permutation runs there.
+gs_status gs_multi::permute_sums(double* image, bool to_image) {
+    DeviceGuard guard;
+    const int64_t W = acc_cam.image_width, H = acc_cam.image_height, tpx = (int64_t)tw * th;
+    const int64_t tx = (W + tw - 1) / tw, nt = tx * ((H + th - 1) / th);
+    std::vector<double> packed((size_t)cap * 3);
+    for (int i = 0; i < (int)dev.size(); i++) {
+        Device& d = dev[i];
+        HIPOK(hipSetDevice(d.id));
+        HIPOK(hipStreamSynchronize(d.stream));
+        if (to_image)
+            HIPOK(hipMemcpy(packed.data(), d.sums.p, packed.size() * 8, hipMemcpyDeviceToHost));
+        else
+            std::fill(packed.begin(), packed.end(), 0.0);
+        const int64_t ns = std::min<int64_t>(rank_slots(i), cap / tpx);
+        for (int64_t sl = 0; sl < ns; sl++) {
+            const int64_t tile = slot_tile(i, sl);
+            if (tile < 0 || tile >= nt) continue;
+            const int64_t x0 = (tile % tx) * tw, y0 = (tile / tx) * th;
+            for (int64_t y = 0; y < th && y0 + y < H; y++) {
+                const int64_t nx = std::min<int64_t>(tw, W - x0);
+                double* img = image + ((y0 + y) * W + x0) * 3;
+                double* pk = packed.data() + (sl * tpx + y * tw) * 3;
+                if (to_image)
+                    std::memcpy(img, pk, (size_t)nx * 24);
+                else
+                    std::memcpy(pk, img, (size_t)nx * 24);
+            }
+        }
+        if (!to_image) HIPOK(hipMemcpy(d.sums.p, packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
+    }
+    return GS_OK;
+}
+
 extern "C" {
+
+gs_status gs_multi_accum_begin(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk) {
+    if (!m || !cam) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    return m->accum_begin(cam, seed, chunk);
+}
+
+gs_status gs_multi_accum_pass(gs_multi* m, uint32_t samples, const gs_multi_outputs* out, gs_stats* stats) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->acc_open) return fail(GS_ERR_ARG, "no accumulation is open: gs_multi_accum_begin first");
+    const uint32_t c = m->acc_chunk;
+    if (samples == 0 || samples % c != 0 || samples / c > 64u)
+        return fail(GS_ERR_ARG, "a pass is 1 to 64 whole chunks of samples");
+    if (m->acc_samples + samples > 0xFFFFFFFFull) return fail(GS_ERR_ARG, "the frame's samples overflow 32 bits");
+    const gs_sample_settings ss{0.0, 0.0, samples, 0};
+    return m->render(&m->acc_cam, &ss, m->acc_seed, out, stats, samples);
+}
+
+gs_status gs_multi_accum_info(const gs_multi* m, gs_accum_info* info) {
+    if (!m || !info) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->acc_open) return fail(GS_ERR_ARG, "no accumulation is open");
+    std::memset(info, 0, sizeof(*info));
+    info->width = m->acc_cam.image_width;
+    info->height = m->acc_cam.image_height;
+    info->chunk = m->acc_chunk;
+    info->passes = m->acc_passes;
+    info->seed = m->acc_seed;
+    info->samples = m->acc_samples;
+    info->last_delta = m->acc_last_delta;
+    info->counters = m->acc_counters;
+    return GS_OK;
+}
+
+gs_status gs_multi_accum_download(gs_multi* m, double* sums) {
+    if (!m || !sums) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->acc_open) return fail(GS_ERR_ARG, "no accumulation is open");
+    return m->permute_sums(sums, true);
+}
+
+gs_status gs_multi_accum_upload(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk, uint64_t samples,
+                                const double* sums, const gs_counters* counters) {
+    if (!m || !cam || !sums || !counters) return fail(GS_ERR_ARG, "null argument");
+    const uint32_t c = chunk ? chunk : 16u;
+    if (samples % c != 0 || samples > 0xFFFFFFFFull)
+        return fail(GS_ERR_ARG, "a checkpoint's samples are whole chunks, below 2^32");
+    std::lock_guard<std::mutex> lock(m->mu);
+    gs_status s = m->accum_begin(cam, seed, chunk);
+    if (s != GS_OK) return s;
+    s = m->permute_sums(const_cast<double*>(sums), false);
+    if (s != GS_OK) {
+        m->accum_end();
+        return s;
+    }
+    m->acc_samples = samples;
+    m->acc_counters = *counters;
+    return GS_OK;
+}
+
+gs_status gs_multi_accum_end(gs_multi* m) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->acc_open) return fail(GS_ERR_ARG, "no accumulation is open");
+    m->accum_end();
+    return GS_OK;
+}
 
 const char* gs_rccl_library(void) {
     const Rccl& r = rccl();
@@ -511,6 +720,7 @@ gs_status gs_multi_create(const gs_flat_scene* scene, const gs_launch* launch, g
 gs_status gs_multi_render(gs_multi* m, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                           const gs_multi_outputs* out, gs_stats* stats) {
     if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
     return m->render(cam, ss, seed, out, stats);
 }
 
@@ -562,7 +772,10 @@ gs_status gs_render_multi(const gs_flat_scene* scene, const gs_camera* cam, cons
     gs_status s = gs_multi_create(scene, launch, &m);
     if (s != GS_OK) return s;
     const auto t1 = std::chrono::steady_clock::now();
-    s = m->render(cam, ss, seed, out, stats);
+    {
+        std::lock_guard<std::mutex> lock(m->mu);
+        s = m->render(cam, ss, seed, out, stats);
+    }
     gs_multi_destroy(m);
     if (s == GS_OK && stats) {
         stats->setup_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();

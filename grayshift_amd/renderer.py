@@ -1,15 +1,19 @@
 """Python entry points to the device path (libgrayshift.so, HIP for gfx950).
 
 * ``render(scene)`` — the one-call ``Camera::render`` replacement (linear f32 frame).
+* ``ProgressiveRenderer`` — a fixed-spp frame as a sequence of passes over device-resident
+  f64 sums: preview, add samples, checkpoint, resume (bit-identical to the one-shot render).
 * ``Renderer`` — device-resident scene for repeated / multi-GPU rendering: upload once,
   render this rank's tiles into a caller-provided device buffer on a given stream.
   Used by bench.py with torch tensors as the device buffers (torch is plumbing only).
 """
 import ctypes as C
+import time
 
 import numpy as np
 
 from . import _native as N
+from . import checkpoint
 
 
 def camera(cam_spec):
@@ -180,6 +184,179 @@ class MultiRenderer:
             pass
 
 
+class ProgressiveRenderer:
+    """A fixed-spp frame rendered in passes (gs_multi_accum_*): every pass adds `samples` more
+    samples per pixel to f64 sums resident on the devices and returns the frame resolved so far.
+
+    The contract: passes of n_1, n_2, ... samples give the frame, the sums and the cumulative
+    counters of one render of n_1 + n_2 + ... samples with the same seed and chunk, bit for bit
+    -- however the samples are split into passes, on any number of GPUs, and across save() /
+    resume().  The scene's own SampleSettings are not used: a pass is a sample count (adaptive
+    sampling has no pass form).  chunk: the coarse sample chunk c (0 = 16); every pass is 1 to
+    64 whole chunks."""
+
+    def __init__(self, scene, num_gpus=1, seed=1, chunk=0, tile=64, plan=True, devices=None, _resume=None):
+        self.scene = scene
+        self.seed = int(seed)
+        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=plan, devices=devices)
+        self._open = False
+        self._passes0 = 0
+        self._delta0 = 0.0
+        try:
+            if _resume is None:
+                N.check(N.lib.gs_multi_accum_begin(self._mr.handle, C.byref(self._mr.cam), self.seed, int(chunk)))
+            else:
+                sums, meta = _resume
+                cnt = N.gs_counters(**meta["counters"])
+                N.check(N.lib.gs_multi_accum_upload(self._mr.handle, C.byref(self._mr.cam), self.seed, int(chunk),
+                                                    meta["samples"], sums.ctypes.data, C.byref(cnt)))
+                self._passes0 = meta.get("passes", 0)
+                self._delta0 = meta.get("last_delta", 0.0)
+            self._open = True
+            self.chunk = self._info().chunk
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def width(self):
+        return self._mr.width
+
+    @property
+    def height(self):
+        return self._mr.height
+
+    @property
+    def devices(self):
+        return self._mr.devices
+
+    def _info(self):
+        i = N.gs_accum_info()
+        N.check(N.lib.gs_multi_accum_info(self._mr.handle, C.byref(i)))
+        return i
+
+    @property
+    def samples(self):
+        """Samples per pixel accumulated so far."""
+        return int(self._info().samples)
+
+    def info(self):
+        """width, height, chunk, passes, seed, samples, last_delta (the last pass's mean |change|
+        of the f64 colour over W*H*3 values) and the cumulative counters.  After resume(), passes
+        continues the checkpoint's count, and last_delta is the checkpoint's until a pass runs."""
+        d = self._info().as_dict()
+        if d["passes"] == 0:
+            d["last_delta"] = self._delta0
+        d["passes"] += self._passes0
+        return d
+
+    def render_pass(self, samples, rgb=True, rgb8=False, ppm=False):
+        """Render `samples` more samples of every pixel (1 to 64 whole chunks) and resolve the frame.
+        Returns a dict: the requested outputs ("rgb" [H,W,3] f32, "rgb8", "ppm"; with none the f32
+        frame stays on the first device, frame_ptr()), this pass's "counters" and "stats", and
+        "info" (info() after the pass)."""
+        out, res, ppm_buf = _outputs(self.width, self.height, rgb, rgb8, ppm)
+        st = N.gs_stats()
+        N.check(N.lib.gs_multi_accum_pass(self._mr.handle, int(samples), C.byref(out) if out is not None else None,
+                                          C.byref(st)))
+        if ppm:
+            res["ppm"] = ppm_buf[0].raw[:ppm_buf[1].value]
+        res["counters"] = st.counters.as_dict()
+        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+        res["info"] = self.info()
+        return res
+
+    def render_until(self, total_samples=None, seconds=None, min_delta=None, pass_samples=None, on_pass=None):
+        """Run passes until the first bound is reached: the frame holds `total_samples` samples per
+        pixel (a multiple of the chunk), `seconds` of wall time have passed since the call, or a
+        pass's last_delta is at most `min_delta`.  pass_samples: samples per pass, rounded up to
+        whole chunks and capped at 64 chunks (default: 4 chunks).  on_pass(info, frame) is called
+        after every pass with info() and the resolved [H,W,3] f32 frame (a preview).  Returns
+        (info, frame) of the last pass; frame is None when no pass ran."""
+        if total_samples is None and seconds is None and min_delta is None:
+            raise ValueError("render_until needs a bound: total_samples, seconds or min_delta")
+        c = self.chunk
+        if total_samples is not None and total_samples % c:
+            raise ValueError("total_samples %d is not a multiple of the chunk %d" % (total_samples, c))
+        step = 4 * c if pass_samples is None else int(pass_samples)
+        step = min(64 * c, max(c, (step + c - 1) // c * c))
+        t0 = time.monotonic()
+        info, frame = self.info(), None
+        while True:
+            n = step
+            if total_samples is not None:
+                n = min(n, total_samples - info["samples"])
+                if n <= 0:
+                    break
+            if seconds is not None and frame is not None and time.monotonic() - t0 >= seconds:
+                break
+            res = self.render_pass(n)
+            info, frame = res["info"], res["rgb"]
+            if on_pass is not None:
+                on_pass(info, frame)
+            if min_delta is not None and info["last_delta"] <= min_delta:
+                break
+            if seconds is not None and time.monotonic() - t0 >= seconds:
+                break
+        return info, frame
+
+    def sums(self):
+        """The running sums, [H, W, 3] f64 in image order (a copy on the host)."""
+        out = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        N.check(N.lib.gs_multi_accum_download(self._mr.handle, out.ctypes.data))
+        return out
+
+    def frame_ptr(self):
+        """(device pointer of the last resolved W*H*3 f32 frame or None, its device id)."""
+        return self._mr.frame_ptr()
+
+    def scene_info(self, rank=0):
+        return self._mr.scene_info(rank)
+
+    def save(self, path):
+        """Write a checkpoint (grayshift_amd.checkpoint): the sums, samples, seed, chunk, frame size,
+        the gs_camera bytes and the cumulative counters."""
+        i = self.info()
+        meta = {k: i[k] for k in ("samples", "seed", "chunk", "width", "height", "counters", "passes", "last_delta")}
+        meta["camera"] = bytes(self._mr.cam)
+        checkpoint.write_checkpoint(path, self.sums(), meta)
+
+    @classmethod
+    def resume(cls, scene, path, **kw):
+        """Continue the checkpoint at `path` on `scene`: **kw as for the constructor (any device
+        count or tile plan).  seed and chunk default to the checkpoint's; the checkpoint is
+        rejected (checkpoint.CheckpointError) when its frame size, chunk, seed or gs_camera bytes
+        differ from the scene's and the ones given.  Whether `scene` is otherwise the world the
+        checkpoint was rendered from is the caller's responsibility."""
+        sums, meta = checkpoint.read_checkpoint(path)
+        cam = camera(scene.camera)
+        seed = kw.pop("seed", meta["seed"])
+        chunk = kw.pop("chunk", meta["chunk"]) or 16
+        checkpoint.check_compatible(meta, cam.image_width, cam.image_height, chunk, seed, bytes(cam))
+        return cls(scene, seed=seed, chunk=chunk, _resume=(sums, meta), **kw)
+
+    def close(self):
+        mr = getattr(self, "_mr", None)
+        if mr is not None:
+            if self._open and mr.handle:
+                N.lib.gs_multi_accum_end(mr.handle)
+            self._open = False
+            mr.close()
+            self._mr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
+            pass
+
+
 def ppm_encode_async(d_rgb8, width, height, d_text, text_capacity, d_len, d_scratch, scratch_bytes, stream=0):
     """Format a device W*H*3 byte frame as the reference's PPM text on the device."""
     N.check(N.lib.gs_ppm_encode_async(C.c_void_p(d_rgb8), width, height, C.c_void_p(d_text), text_capacity,
@@ -305,6 +482,18 @@ class Renderer:
         N.check(N.lib.gs_render_tiles_ex_async(self.dev, C.byref(self.cam), C.byref(self.settings), seed,
                                                C.byref(self.part), C.byref(o), C.c_void_p(d_counters),
                                                C.c_void_p(stream)))
+
+    def render_pass_async(self, samples, sample_base, d_sums, d_rgb=0, d_rgb8=0, d_counters=0, stream=0, seed=1,
+                          chunk=0):
+        """One progressive pass of this rank's tiles (gs_render_tiles_pass_async): samples
+        [sample_base, sample_base + samples) are added to d_sums (device, capacity*3 f64, zeroed by
+        the caller before the first pass) and d_sums / (sample_base + samples) is written to d_rgb
+        (capacity*3 f32) and / or d_rgb8.  chunk: the coarse chunk, 0 = 16; samples and sample_base
+        are multiples of it.  The scene's own SampleSettings are not used."""
+        o = N.gs_render_outputs(d_rgb or None, d_rgb8 or None, None)
+        N.check(N.lib.gs_render_tiles_pass_async(self.dev, C.byref(self.cam), samples, seed, C.byref(self.part),
+                                                 sample_base, chunk, C.c_void_p(d_sums), C.byref(o),
+                                                 C.c_void_p(d_counters), C.c_void_p(stream)))
 
     def unpack_u8_async(self, d_gathered, d_frame, world_size, stream=0):
         part = N.gs_partition(0, world_size, self.part.tile_w, self.part.tile_h, self.part.d_tile_order,

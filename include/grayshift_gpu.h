@@ -499,6 +499,68 @@ gs_status gs_debug_set_multi_collective(int32_t always);
  * unpack, the summed counters, per-rank frame notes) with N scenes on one device; 0 (default). */
 gs_status gs_debug_set_multi_same_device(int32_t on);
 
+/* ---- Progressive rendering (additive: the ABI stays 11, no existing call changes) ----
+ * A fixed-spp frame as a sequence of passes over device-resident f64 sums: render n samples,
+ * look at the frame, render n more, checkpoint, resume.
+ *
+ * The contract: sample s of a pixel draws from stream_seed(seed, pixel, s) whichever launch
+ * runs it, and a pixel's sum is ((0 + C_0) + C_1) + ... over chunk sums of `chunk` samples
+ * taken in sample order.  A pass continues that sum where the last one stopped, so passes of
+ * n_1, n_2, ... samples (each a multiple of `chunk`) leave the sums, the linear f32 frame, the
+ * rgb8 frame and the cumulative counters of ONE render of n_1 + n_2 + ... samples with the same
+ * seed and chunk, bit for bit -- for any split into passes, any device count or tile plan, and
+ * across a checkpoint.  That one render is gs_multi_render / gs_render at a fixed spp whose
+ * coarse chunk is `chunk` (e.g. gs_set_tuning(.., sample_chunk = chunk) with spp / chunk <= 64).
+ * Adaptive settings have no pass form: a pass is a sample count.
+ *
+ * The tile-level primitive, stateless: renders samples [sample_base, sample_base + samples) of
+ * this rank's packed pixels, adds them to d_sums (device, capacity*3 f64 in packed order, owned
+ * by the caller and zeroed before the first pass) and writes d_sums / (sample_base + samples) to
+ * out->rgb / out->rgb8 (padding pixels get 0).  chunk: the coarse chunk c, 0 = 16, taken as
+ * given (none of the one-shot render's frame- and size-dependent rules apply); the launch is
+ * always chunked.  GS_ERR_ARG, before any device work, when: an argument is NULL (d_counters
+ * may be), samples == 0, samples or sample_base is not a multiple of c, samples / c > 64, the
+ * pass's chunk sums (capacity * samples / c * 24 bytes) exceed the partial budget (4 GiB), or
+ * sample_base + samples overflows 32 bits.  d_counters is accumulated into; the kernel counts
+ * `pixels` in every pass, so a caller summing passes takes `pixels` from the first alone. */
+gs_status gs_render_tiles_pass_async(const gs_device_scene* scene, const gs_camera* cam, uint32_t samples,
+                                     uint64_t seed, const gs_partition* part, uint32_t sample_base,
+                                     uint32_t chunk, double* d_sums, const gs_render_outputs* out,
+                                     gs_counters* d_counters, void* stream);
+
+/* The frame context's accumulation.  gs_multi_accum_begin fixes the camera, the seed and the
+ * chunk (0 = 16), computes the tile plan once and allocates zeroed sums on every rank.  Each
+ * gs_multi_accum_pass then renders the next `samples` samples (1 to 64 whole chunks) of every
+ * pixel on every rank and delivers the resolved frame like gs_multi_render: `out` as there, NULL
+ * leaves the frame on the first device (gs_multi_frame); `stats` describes this pass alone.
+ * While an accumulation is open gs_multi_render returns GS_ERR_ARG (its re-plan would
+ * invalidate the packed sums); gs_multi_accum_end frees the sums and closes it.  Calls on a
+ * context without an open accumulation return GS_ERR_ARG. */
+typedef struct gs_accum_info {
+    int32_t width, height;
+    uint32_t chunk;       /* the coarse chunk c (resolved: never 0) */
+    uint32_t passes;      /* passes run since gs_multi_accum_begin / _upload */
+    uint64_t seed;
+    uint64_t samples;     /* samples per pixel in the sums */
+    double last_delta;    /* the last pass's change: the mean over W*H*3 values of |colour after - colour
+                             before| (f64 colours; before = 0 for the first pass).  Deterministic: per-block
+                             partial sums on a grid set by the rank's capacity alone, added in index and
+                             rank order -- the same bits run to run; the last bits depend on the device
+                             count (the order of the additions), nothing else does */
+    gs_counters counters; /* cumulative; equal to a one-shot render's (`pixels` counted once) */
+} gs_accum_info;
+gs_status gs_multi_accum_begin(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk);
+gs_status gs_multi_accum_pass(gs_multi* m, uint32_t samples, const gs_multi_outputs* out, gs_stats* stats);
+gs_status gs_multi_accum_info(const gs_multi* m, gs_accum_info* info);
+/* Checkpoints: the sums in image order, [H][W][3] f64 (host), so sums saved on N devices resume
+ * on M.  gs_multi_accum_upload opens an accumulation like _begin and fills it: `samples` (whole
+ * chunks) are in `sums`, `counters` are the cumulative counters saved with them.  Not hot: the
+ * tile permutation runs on the host. */
+gs_status gs_multi_accum_download(gs_multi* m, double* sums);
+gs_status gs_multi_accum_upload(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk, uint64_t samples,
+                                const double* sums, const gs_counters* counters);
+gs_status gs_multi_accum_end(gs_multi* m);
+
 /* Path of the RCCL library gs_render_multi uses (loaded on this call), or NULL. */
 const char* gs_rccl_library(void);
 
