@@ -133,6 +133,23 @@ pub struct gs_stats {
 /// The persistent N-GPU frame context (ABI 6, opaque).
 #[repr(C)] pub struct gs_multi { _private: [u8; 0] }
 
+/// The top bit of a `state` word (gs_multi_adapt_download): the pixel has stopped.
+pub const GS_ADAPT_STOPPED: u32 = 0x8000_0000;
+
+/// Outputs of a progressive adaptive pass, per packed pixel (additive, ABI 11).
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct gs_round_outputs {
+    pub rgb: *mut f32, pub rgb8: *mut u8, pub samples: *mut u32, pub rel_error: *mut f32,
+}
+
+/// An open adaptation of the frame context (progressive adaptive passes; additive, ABI 11).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_adapt_info {
+    pub width: i32, pub height: i32, pub batch: u32, pub rounds: u32, pub max_rounds: u32, pub finished: u32,
+    pub seed: u64, pub active_pixels: u64, pub samples_total: u64, pub samples_max: u64,
+    pub counters: gs_counters,
+}
+
 /// An open accumulation of the frame context (progressive rendering; additive, ABI 11).
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct gs_accum_info {
@@ -235,6 +252,26 @@ extern "C" {
     pub fn gs_multi_accum_upload(m: *mut gs_multi, cam: *const gs_camera, seed: u64, chunk: u32, samples: u64,
                                  sums: *const f64, counters: *const gs_counters) -> gs_status;
     pub fn gs_multi_accum_end(m: *mut gs_multi) -> gs_status;
+    /// Progressive adaptive passes: a frame's batch rounds split over passes, on caller-owned
+    /// state; any split leaves the bits of the one-shot render with the same settings and seed.
+    pub fn gs_round_state_bytes(cam: *const gs_camera, part: *const gs_partition,
+                                ss: *const gs_sample_settings) -> i64;
+    pub fn gs_render_tiles_rounds_async(scene: *const gs_device_scene, cam: *const gs_camera,
+                                        ss: *const gs_sample_settings, seed: u64, part: *const gs_partition,
+                                        first_round: u32, rounds: u32, d_state: *mut c_void, state_bytes: i64,
+                                        out: *const gs_round_outputs, d_counters: *mut gs_counters,
+                                        stream: *mut c_void) -> gs_status;
+    pub fn gs_multi_adapt_begin(m: *mut gs_multi, cam: *const gs_camera, ss: *const gs_sample_settings,
+                                seed: u64) -> gs_status;
+    pub fn gs_multi_adapt_pass(m: *mut gs_multi, rounds: u32, out: *const gs_multi_outputs,
+                               stats: *mut gs_stats) -> gs_status;
+    pub fn gs_multi_adapt_info(m: *const gs_multi, info: *mut gs_adapt_info) -> gs_status;
+    pub fn gs_multi_adapt_maps(m: *mut gs_multi, samples: *mut u32, rel_error: *mut f32) -> gs_status;
+    pub fn gs_multi_adapt_download(m: *mut gs_multi, sums: *mut f64, state: *mut u32) -> gs_status;
+    pub fn gs_multi_adapt_upload(m: *mut gs_multi, cam: *const gs_camera, ss: *const gs_sample_settings, seed: u64,
+                                 rounds_done: u32, sums: *const f64, state: *const u32,
+                                 counters: *const gs_counters) -> gs_status;
+    pub fn gs_multi_adapt_end(m: *mut gs_multi) -> gs_status;
 }
 
 pub fn last_error() -> String {

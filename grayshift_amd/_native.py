@@ -163,6 +163,25 @@ class gs_accum_info(C.Structure):
         return d
 
 
+GS_ADAPT_STOPPED = 0x80000000
+
+
+class gs_round_outputs(C.Structure):
+    _fields_ = [("rgb", C.c_void_p), ("rgb8", C.c_void_p), ("samples", C.c_void_p), ("rel_error", C.c_void_p)]
+
+
+class gs_adapt_info(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("batch", C.c_uint32), ("rounds", C.c_uint32),
+                ("max_rounds", C.c_uint32), ("finished", C.c_uint32), ("seed", C.c_uint64),
+                ("active_pixels", C.c_uint64), ("samples_total", C.c_uint64), ("samples_max", C.c_uint64),
+                ("counters", gs_counters)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "counters"}
+        d["counters"] = self.counters.as_dict()
+        return d
+
+
 # Every symbol include/*.h declares, with its ctypes signature.
 _P = C.c_void_p
 SIGNATURES = {
@@ -231,6 +250,19 @@ SIGNATURES = {
     "gs_multi_accum_upload": (C.c_int32, [_P, C.POINTER(gs_camera), C.c_uint64, C.c_uint32, C.c_uint64, _P,
                                           C.POINTER(gs_counters)]),
     "gs_multi_accum_end": (C.c_int32, [_P]),
+    "gs_round_state_bytes": (C.c_int64, [C.POINTER(gs_camera), C.POINTER(gs_partition),
+                                         C.POINTER(gs_sample_settings)]),
+    "gs_render_tiles_rounds_async": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,
+                                                 C.POINTER(gs_partition), C.c_uint32, C.c_uint32, _P, C.c_int64,
+                                                 C.POINTER(gs_round_outputs), _P, _P]),
+    "gs_multi_adapt_begin": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64]),
+    "gs_multi_adapt_pass": (C.c_int32, [_P, C.c_uint32, C.POINTER(gs_multi_outputs), C.POINTER(gs_stats)]),
+    "gs_multi_adapt_info": (C.c_int32, [_P, C.POINTER(gs_adapt_info)]),
+    "gs_multi_adapt_maps": (C.c_int32, [_P, _P, _P]),
+    "gs_multi_adapt_download": (C.c_int32, [_P, _P, _P]),
+    "gs_multi_adapt_upload": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,
+                                          C.c_uint32, _P, _P, C.POINTER(gs_counters)]),
+    "gs_multi_adapt_end": (C.c_int32, [_P]),
     # grayshift_host.h
     "gs_host_scene_from_spec": (C.c_int32, [C.POINTER(gs_scene_spec), C.POINTER(_P)]),
     "gs_host_scene_destroy": (C.c_int32, [_P]),

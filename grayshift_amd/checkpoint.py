@@ -15,6 +15,17 @@ A checkpoint holds
 resume on.  Scene identity beyond that -- the world's objects, materials, textures, background --
 is the caller's responsibility: a checkpoint does not fingerprint the world, and resuming it on
 another world with the same camera silently mixes two images.
+
+An adaptive frame in progress (``AdaptiveRenderer``) is format ``ADAPTIVE_FORMAT`` (2):
+
+* ``sums``  -- [H, W, 5] f64: Σr, Σg, Σb, Σlum, Σlum² per pixel, in image order;
+* ``state`` -- [H, W] u32: batches taken, the top bit set once the pixel has stopped;
+* ``rounds``, ``seed``, ``width``, ``height`` -- the rounds run, the RNG seed, the frame size;
+* ``confidence``, ``tolerance``, ``batch_size``, ``max_samples`` -- the SampleSettings;
+* ``camera``, ``counters`` -- as above.
+
+``read_checkpoint`` rejects it, and ``read_adaptive_checkpoint`` rejects format 1: neither
+renderer can resume the other's file.
 """
 import numpy as np
 
@@ -83,5 +94,93 @@ def check_compatible(meta, width, height, chunk, seed, camera):
                              ("chunk", meta["chunk"], int(chunk)), ("seed", meta["seed"], int(seed))):
         if have != want:
             raise CheckpointError("checkpoint %s %d differs from the scene's %d" % (name, have, want))
+    if bytes(meta["camera"]) != bytes(camera):
+        raise CheckpointError("checkpoint camera differs from the scene's")
+
+
+# ------------------------------------------------------------------ adaptive frames (format 2)
+ADAPTIVE_FORMAT = 2
+STOPPED = 0x80000000
+SETTINGS = ("confidence", "tolerance", "batch_size", "max_samples")
+ADAPTIVE_REQUIRED = ("rounds", "seed", "width", "height", "camera", "counters") + SETTINGS
+
+
+def _check_adaptive(sums, state, meta):
+    h, w = meta["height"], meta["width"]
+    if sums.shape != (h, w, 5):
+        raise CheckpointError("sums of shape %r for a %d x %d adaptive frame" % (sums.shape, w, h))
+    if state.shape != (h, w):
+        raise CheckpointError("state of shape %r for a %d x %d frame" % (state.shape, w, h))
+    bs, ms = meta["batch_size"], meta["max_samples"]
+    if bs <= 0 or ms < bs:
+        raise CheckpointError("settings with batch_size %d, max_samples %d are not adaptive" % (bs, ms))
+    if not 0 <= meta["rounds"] <= ms // bs + 1:
+        raise CheckpointError("rounds %d outside the settings' %d" % (meta["rounds"], ms // bs + 1))
+    taken = state & np.uint32(STOPPED - 1)
+    stopped = (state & np.uint32(STOPPED)) != 0
+    if np.any(taken[~stopped] != meta["rounds"]) or np.any(taken[stopped] > meta["rounds"]) or \
+            np.any(taken[stopped] < 1):
+        raise CheckpointError("a pixel's state disagrees with %d rounds" % meta["rounds"])
+
+
+def write_adaptive_checkpoint(path, sums, state, meta):
+    """Write `sums` ([H, W, 5] f64), `state` ([H, W] u32) and `meta` to `path` (a file name, used as
+    given, or a file object).  meta: rounds, seed, width, height, batch_size, max_samples (ints),
+    confidence, tolerance (floats), camera (bytes), counters (a dict by COUNTER_NAMES)."""
+    for k in ADAPTIVE_REQUIRED:
+        if k not in meta:
+            raise CheckpointError("checkpoint meta lacks %r" % k)
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    state = np.ascontiguousarray(state, dtype=np.uint32)
+    m = {k: int(meta[k]) for k in ("rounds", "seed", "width", "height", "batch_size", "max_samples")}
+    _check_adaptive(sums, state, m)
+    counters = np.array([int(meta["counters"][n]) for n in COUNTER_NAMES], dtype=np.uint64)
+    fields = dict(format=np.int64(ADAPTIVE_FORMAT), sums=sums, state=state, rounds=np.uint32(m["rounds"]),
+                  seed=np.uint64(m["seed"]), width=np.int32(m["width"]), height=np.int32(m["height"]),
+                  confidence=np.float64(meta["confidence"]), tolerance=np.float64(meta["tolerance"]),
+                  batch_size=np.uint32(m["batch_size"]), max_samples=np.uint32(m["max_samples"]),
+                  camera=np.frombuffer(bytes(meta["camera"]), dtype=np.uint8), counters=counters)
+    if hasattr(path, "write"):
+        np.savez(path, **fields)
+    else:
+        with open(path, "wb") as f:  # (the name as given: numpy would add ".npz" to it)
+            np.savez(f, **fields)
+
+
+def read_adaptive_checkpoint(path):
+    """-> (sums [H, W, 5] f64, state [H, W] u32, meta) as write_adaptive_checkpoint took them."""
+    with np.load(path, allow_pickle=False) as z:
+        if "format" not in z.files or int(z["format"]) != ADAPTIVE_FORMAT:
+            raise CheckpointError("not a grayshift adaptive checkpoint (format %d)" % ADAPTIVE_FORMAT)
+        for k in ADAPTIVE_REQUIRED + ("sums", "state"):
+            if k not in z.files:
+                raise CheckpointError("checkpoint lacks %r" % k)
+        sums = np.ascontiguousarray(z["sums"], dtype=np.float64)
+        state = np.ascontiguousarray(z["state"], dtype=np.uint32)
+        meta = {"rounds": int(z["rounds"]), "seed": int(z["seed"]), "width": int(z["width"]),
+                "height": int(z["height"]), "confidence": float(z["confidence"]), "tolerance": float(z["tolerance"]),
+                "batch_size": int(z["batch_size"]), "max_samples": int(z["max_samples"]),
+                "camera": z["camera"].tobytes(),
+                "counters": {n: int(v) for n, v in zip(COUNTER_NAMES, z["counters"])}}
+    _check_adaptive(sums, state, meta)
+    return sums, state, meta
+
+
+def check_adaptive_compatible(meta, width, height, settings, seed, camera):
+    """Raise CheckpointError unless the checkpoint's size, seed, camera bytes and the four
+    SampleSettings fields are the ones given.  settings: an object with confidence, tolerance,
+    batch_size and max_samples (a gs_sample_settings), or a dict of them.  Floats compare by
+    value of the f64; the world itself is not compared."""
+    def get(k):
+        return settings[k] if isinstance(settings, dict) else getattr(settings, k)
+    for name, have, want in (("width", meta["width"], int(width)), ("height", meta["height"], int(height)),
+                             ("seed", meta["seed"], int(seed)),
+                             ("batch_size", meta["batch_size"], int(get("batch_size"))),
+                             ("max_samples", meta["max_samples"], int(get("max_samples")))):
+        if have != want:
+            raise CheckpointError("checkpoint %s %d differs from the scene's %d" % (name, have, want))
+    for name in ("confidence", "tolerance"):
+        if np.float64(meta[name]).tobytes() != np.float64(get(name)).tobytes():
+            raise CheckpointError("checkpoint %s %r differs from the scene's %r" % (name, meta[name], get(name)))
     if bytes(meta["camera"]) != bytes(camera):
         raise CheckpointError("checkpoint camera differs from the scene's")

@@ -275,7 +275,17 @@ struct KParams {
     double* accum;
     // [gs_accum_blocks(capacity)] per-block sums of |colour after - colour before| (nullable)
     double* delta;
+    // Progressive adaptive passes (gs_render_tiles_rounds_async; DESIGN.md §3.2 "Progressive
+    // adaptive passes"): the round state (round_counts, the lists, pstate) lives in the caller's
+    // blob, every round has split items, and gs_round_fold_kernel takes gs_round_combine_kernel's
+    // place: it keeps a stopped pixel's final sums in pstate too and writes no colour.
+    // gs_round_resolve_kernel ends the pass.  Every other launch leaves these null.
+    uint32_t* pbatches;       // per packed pixel: batches taken, GS_ADAPT_STOPPED once it has stopped
+    uint32_t* map_samples;    // per packed pixel: samples taken so far (nullable)
+    float* map_error;         // per packed pixel: the stop test's relative error (nullable)
+    unsigned long long* round_summary;  // [GS_ROUND_SUMMARY_WORDS]: active pixels, Σ samples, max samples, 0
 };
+#define GS_ROUND_SUMMARY_WORDS 4
 
 // gs_accumulate_kernel's grid: one block of 256 per 256 packed pixels up to 2048 blocks (a
 // grid-stride loop past that) -- a function of the capacity alone, so the per-block partial

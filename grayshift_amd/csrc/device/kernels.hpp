@@ -18,4 +18,8 @@ hipError_t launch_round_init_kernel(hipStream_t st, unsigned grid, const KParams
 hipError_t launch_round_params_kernel(hipStream_t st, KParams* P, uint32_t round, uint32_t seg, uint32_t seg_px,
                                       int32_t chunk_req, int32_t whole_mode);
 hipError_t launch_round_combine_kernel(hipStream_t st, unsigned grid, const KParams* P, uint32_t round);
+// (a progressive adaptive pass: the fold after each (round, segment) launch, the resolve at the
+// pass's end on gs_accum_blocks(capacity) blocks)
+hipError_t launch_round_fold_kernel(hipStream_t st, unsigned grid, const KParams* P, uint32_t round);
+hipError_t launch_round_resolve_kernel(hipStream_t st, const KParams* P, uint32_t capacity);
 hipError_t launch_render_kernel(hipStream_t st, void (*kernel)(KArgs), unsigned blocks, size_t lds, const KArgs& a);

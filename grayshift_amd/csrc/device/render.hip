@@ -2639,6 +2639,153 @@ __global__ void gs_round_combine_kernel(const KParams* __restrict__ P, uint32_t 
     }
 }
 
+// ------------------------------------------------ progressive adaptive passes
+// A frame's rounds split over passes (gs_render_tiles_rounds_async): the round state lives in
+// the caller's blob and every round has split items, so the megakernel never touches it.
+
+// gs_round_combine_kernel for a pass: the same additions in the same order and the same stop
+// test, but a stopped pixel's final sums are kept too, with its batches-taken word
+// (GS_ADAPT_STOPPED set), and no colour is written: gs_round_resolve_kernel resolves every
+// pixel from its sums at the end of the pass.
+__global__ void gs_round_fold_kernel(const KParams* __restrict__ P, uint32_t round) {
+    const uint32_t n = P->seg_n, bs = P->ss.batch_size, lane = threadIdx.x & 63u;
+    const uint32_t span = (n + 63u) & ~63u;
+    const double confidence_sq = P->ss.confidence * P->ss.confidence;
+    const double tolerance_sq = P->ss.tolerance * P->ss.tolerance;
+    const double scount = (double)((uint64_t)(round + 1u) * bs);
+    for (uint32_t a = blockIdx.x * blockDim.x + threadIdx.x; a < span; a += gridDim.x * blockDim.x) {
+        bool go_on = false, stopped = false;
+        uint32_t item = 0;
+        if (a < n) {
+            item = P->active[P->seg_base + a];
+            double* ps = P->pstate + (size_t)item * 5;
+            double r = 0.0, g = 0.0, b = 0.0, lsum = 0.0, lsq = 0.0;
+            if (round) {
+                r = ps[0];
+                g = ps[1];
+                b = ps[2];
+                lsum = ps[3];
+                lsq = ps[4];
+            }
+            const double* smp = P->partial + (size_t)a * (GS_ROUND_PIXEL_MAJOR ? bs : 1u) * 3;
+            for (uint32_t j = 0; j < bs; j++, smp += (GS_ROUND_PIXEL_MAJOR ? 1u : (size_t)n) * 3) {
+                const double cr = smp[0], cg = smp[1], cb = smp[2];
+                r += cr;
+                g += cg;
+                b += cb;
+                const double lum = 0.299 * cr + 0.587 * cg + 0.144 * cb;
+                lsum += lum;
+                lsq += lum * lum;
+            }
+            const double mean = lsum / scount;
+            const double variance_sq = 1.0 / (scount - 1.0) * (lsq - lsum * lsum / scount);
+            const double convergence_sq = confidence_sq * variance_sq / scount;
+            bool stop = convergence_sq < (mean * mean * tolerance_sq);
+            if (!stop) stop = (uint32_t)sat_u64(scount, 4294967295.0, 4294967295ull) > P->ss.max_samples;
+            ps[0] = r;
+            ps[1] = g;
+            ps[2] = b;
+            ps[3] = lsum;
+            ps[4] = lsq;
+            P->pbatches[item] = (round + 1u) | (stop ? GS_ADAPT_STOPPED : 0u);
+            stopped = stop;
+            go_on = !stop;
+        }
+        const uint64_t mg = __builtin_amdgcn_ballot_w64(go_on), ms = __builtin_amdgcn_ballot_w64(stopped);
+        if (mg != 0) {
+            const uint32_t leader = (uint32_t)__builtin_ctzll(mg);
+            uint32_t base = 0;
+            if (lane == leader) base = atomicAdd(&P->round_counts[round + 1u], (uint32_t)__popcll(mg));
+            base = __shfl(base, (int)leader);
+            if (go_on) P->next_active[base + (uint32_t)__popcll(mg & ((1ull << lane) - 1ull))] = item;
+        }
+        if (ms != 0 && P->counters && lane == (uint32_t)__builtin_ctzll(ms))
+            atomicAdd(&P->counters[C_PIX], (unsigned long long)__popcll(ms));
+    }
+}
+
+// The end of a pass, over every packed pixel of the rank: a pixel's colour is its Σrgb over the
+// samples it has taken -- the combine's `r / scount` for a stopped pixel, the preview for an
+// active one -- so an output buffer never seen before is filled whole; padding slots get zeros
+// (`direct`: as gs_accumulate_kernel).  The maps, when asked for: the samples taken and the
+// stop test's left side as a relative error, sqrt(confidence² · var / n / mean²), from the
+// stored Σlum, Σlum².  The block folds its threads' active pixels, Σ samples and max samples
+// through LDS in a fixed tree; thread 0 adds them to round_summary with integer atomics (the
+// host zeroes it before the kernel), so the totals do not depend on any order.
+__global__ __launch_bounds__(256) void gs_round_resolve_kernel(const KParams* __restrict__ P) {
+    __shared__ uint32_t s_act[256];
+    __shared__ unsigned long long s_sum[256], s_max[256];
+    const uint32_t bs = P->ss.batch_size;
+    const double confidence_sq = P->ss.confidence * P->ss.confidence;
+    uint32_t n_act = 0;
+    unsigned long long n_sum = 0, n_max = 0;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < P->capacity; k += gridDim.x * blockDim.x) {
+        uint32_t pi = 0, pj = 0;
+        const bool real = packed_pixel(P, k, pi, pj);
+        const size_t oi = P->direct ? (size_t)pj * (uint32_t)P->cam.image_width + pi : (size_t)k;
+        float* o = P->out ? P->out + oi * 3 : nullptr;
+        uint8_t* o8 = P->out8 ? P->out8 + oi * 3 : nullptr;
+        if (!real) {
+            if (P->map_samples) P->map_samples[k] = 0u;
+            if (P->map_error) P->map_error[k] = 0.0f;
+            if (P->direct) continue;
+            if (o) {
+                o[0] = 0.0f;
+                o[1] = 0.0f;
+                o[2] = 0.0f;
+            }
+            if (o8) {
+                o8[0] = 0;
+                o8[1] = 0;
+                o8[2] = 0;
+            }
+            continue;
+        }
+        const uint32_t word = P->pbatches[k];
+        const unsigned long long taken = (unsigned long long)(word & ~GS_ADAPT_STOPPED) * bs;
+        const double* ps = P->pstate + (size_t)k * 5;
+        const double scount = (double)taken;
+        const double cr = ps[0] / scount, cg = ps[1] / scount, cb = ps[2] / scount;
+        if (o) {
+            o[0] = (float)cr;
+            o[1] = (float)cg;
+            o[2] = (float)cb;
+        }
+        if (o8) {
+            o8[0] = color_byte(cr);
+            o8[1] = color_byte(cg);
+            o8[2] = color_byte(cb);
+        }
+        if (P->map_samples) P->map_samples[k] = taken > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)taken;
+        if (P->map_error) {
+            const double lsum = ps[3], lsq = ps[4];
+            const double mean = lsum / scount;
+            const double var = 1.0 / (scount - 1.0) * (lsq - lsum * lsum / scount);
+            P->map_error[k] = (float)sqrt(confidence_sq * var / scount / (mean * mean));
+        }
+        n_act += (word & GS_ADAPT_STOPPED) ? 0u : 1u;
+        n_sum += taken;
+        n_max = taken > n_max ? taken : n_max;
+    }
+    s_act[threadIdx.x] = n_act;
+    s_sum[threadIdx.x] = n_sum;
+    s_max[threadIdx.x] = n_max;
+    __syncthreads();
+    for (uint32_t h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) {
+            s_act[threadIdx.x] += s_act[threadIdx.x + h];
+            s_sum[threadIdx.x] += s_sum[threadIdx.x + h];
+            s_max[threadIdx.x] = s_max[threadIdx.x] > s_max[threadIdx.x + h] ? s_max[threadIdx.x] : s_max[threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && P->round_summary) {
+        atomicAdd(&P->round_summary[0], (unsigned long long)s_act[0]);
+        atomicAdd(&P->round_summary[1], s_sum[0]);
+        atomicMax(&P->round_summary[2], s_max[0]);
+    }
+}
+
 // =============================================================== the kernel table and launchers
 // (kernels.hpp; everything else on the host side lives in csrc/host/scene.cpp and launch.cpp)
 void (*kernel_for(int feat))(KArgs) {
@@ -2725,6 +2872,14 @@ hipError_t launch_round_params_kernel(hipStream_t st, KParams* P, uint32_t round
 }
 hipError_t launch_round_combine_kernel(hipStream_t st, unsigned grid, const KParams* P, uint32_t round) {
     hipLaunchKernelGGL(gs_round_combine_kernel, dim3(grid), dim3(256), 0, st, P, round);
+    return hipGetLastError();
+}
+hipError_t launch_round_fold_kernel(hipStream_t st, unsigned grid, const KParams* P, uint32_t round) {
+    hipLaunchKernelGGL(gs_round_fold_kernel, dim3(grid), dim3(256), 0, st, P, round);
+    return hipGetLastError();
+}
+hipError_t launch_round_resolve_kernel(hipStream_t st, const KParams* P, uint32_t capacity) {
+    hipLaunchKernelGGL(gs_round_resolve_kernel, dim3(gs_accum_blocks(capacity)), dim3(256), 0, st, P);
     return hipGetLastError();
 }
 hipError_t launch_render_kernel(hipStream_t st, void (*kernel)(KArgs), unsigned blocks, size_t lds, const KArgs& a) {

@@ -29,6 +29,24 @@ gs_status gs_render_tiles_pass_timed_async(const gs_device_scene* ds, const gs_c
                                            hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters);
 int64_t gs_pass_delta_blocks(int64_t capacity);
 
+// gs_render_tiles_rounds_async with the same extras.  rounds == 0 (this form only) renders
+// nothing and resolves the state as it stands.  After the call's work the blob's summary words
+// (GsRoundLayout::summary) hold this rank's active pixels, Σ samples and max samples of a pixel.
+gs_status gs_render_tiles_rounds_timed_async(const gs_device_scene* ds, const gs_camera* cam,
+                                             const gs_sample_settings* ss, uint64_t seed, const gs_partition* part,
+                                             uint32_t first_round, uint32_t rounds, void* d_state, int64_t state_bytes,
+                                             const gs_round_outputs* out, gs_counters* d_counters, void* stream,
+                                             hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters);
+// The round-state blob of `cap` packed pixels and R rounds, byte offsets (256-B aligned but the
+// first three): the item-size hint, the summary (4 u64), round_counts[R + 2], the two active
+// lists (cap u32 each), pstate (cap * 5 f64), the batches words (cap u32).  Private to the
+// library: the frame context fills and reads it for checkpoints.
+static const int kRoundSummaryWords = 4;  // (kernel_abi.hpp GS_ROUND_SUMMARY_WORDS)
+struct GsRoundLayout {
+    size_t hint, summary, counts, list[2], pstate, batches, bytes;
+};
+GsRoundLayout gs_round_layout(uint64_t cap, uint64_t R);
+
 // The placement pilots still pending for a launch of `cam` / `ss` on n devices (scenes[i] on
 // devices[i], its stream streams[i]): every device's pilot is launched before any is waited
 // for, so the first frame of an N-GPU context pilots concurrently (launch.cpp).  *ran: whether

@@ -218,10 +218,19 @@ struct PassArgs {
     double* d_sums;
     double* d_delta;  // [gs_accum_blocks(capacity)], nullable
 };
+// A progressive adaptive pass (gs_render_tiles_rounds_async): the launch renders rounds
+// [first_round, first_round + rounds) on the round state in the caller's blob, in split items,
+// gs_round_fold_kernel after each; gs_round_resolve_kernel ends it.
+struct RoundArgs {
+    uint32_t first_round, rounds, R;
+    uint8_t* d_state;
+    uint32_t* map_samples;
+    float* map_error;
+};
 static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                         const gs_partition* part, const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
                         hipEvent_t k_begin, hipEvent_t k_end, const VisitArgs* va, bool direct = false,
-                        bool zero_counters = false, const PassArgs* pass = nullptr);
+                        bool zero_counters = false, const PassArgs* pass = nullptr, const RoundArgs* ra = nullptr);
 static gs_status ensure_placement(gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss,
                                   void* stream);
 
@@ -273,6 +282,88 @@ extern "C" gs_status gs_render_tiles_pass_async(const gs_device_scene* ds, const
                                                 gs_counters* d_counters, void* stream) {
     return gs_render_tiles_pass_timed_async(ds, cam, samples, seed, part, sample_base, chunk, d_sums, nullptr, outs,
                                             d_counters, stream, nullptr, nullptr, false, false);
+}
+
+// ---------------------------------------------------------------- progressive adaptive passes
+static_assert(kRoundSummaryWords == GS_ROUND_SUMMARY_WORDS, "the summary words of internal.hpp and kernel_abi.hpp");
+GsRoundLayout gs_round_layout(uint64_t cap, uint64_t R) {
+    const auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    GsRoundLayout l{};
+    l.hint = 0;
+    l.summary = 16;
+    l.counts = 16 + GS_ROUND_SUMMARY_WORDS * 8;
+    l.list[0] = al(l.counts + (size_t)(R + 2) * 4);
+    l.list[1] = l.list[0] + al((size_t)cap * 4);
+    l.pstate = l.list[1] + al((size_t)cap * 4);
+    l.batches = l.pstate + al((size_t)cap * 5 * sizeof(double));
+    l.bytes = l.batches + al((size_t)cap * 4);
+    return l;
+}
+
+// Pixels per segment of a round: as many as the partial budget holds a batch's colours for.
+static uint64_t round_seg_px(uint64_t cap, const gs_sample_settings& ss, const Knobs& k) {
+    uint64_t sp = std::min<uint64_t>(cap, k.partial_budget / ((uint64_t)ss.batch_size * 24u));
+    return std::min<uint64_t>(sp, (0x7FFFFFFFull - 1u) / ss.batch_size);  // (sp * bs < 2^31: the queue's items)
+}
+
+// The checks of a progressive adaptive pass, all on the arguments alone: nothing here reads the
+// scene or touches a device.  zero_rounds: the library's own resolve-only form.
+static gs_status check_rounds(const gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss,
+                              const gs_partition* part, uint32_t first_round, uint32_t rounds, const void* d_state,
+                              int64_t state_bytes, const gs_round_outputs* out, bool zero_rounds) {
+    if (!ds || !cam || !ss || !part || !d_state || !out || (!out->rgb && !out->rgb8))
+        return fail(GS_ERR_ARG, "null argument");
+    const int64_t cap = gs_partition_capacity(cam, part);
+    if (cap < 0 || cap >= (int64_t)0xFFFFFFFFll) return fail(GS_ERR_ARG, "bad partition / image size");
+    if (rounds == 0 && !zero_rounds) return fail(GS_ERR_ARG, "a pass of 0 rounds");
+    if (ss->batch_size == 0) return fail(GS_ERR_ARG, "batch_size 0 never terminates (camera.rs:137)");
+    if (ss->max_samples < ss->batch_size)
+        return fail(GS_ERR_ARG, "the settings run one batch (max_samples < batch_size): a fixed-spp frame has its "
+                                "passes in gs_render_tiles_pass_async");
+    const uint64_t R = (uint64_t)ss->max_samples / ss->batch_size + 1u;
+    if (R > kMaxRounds) return fail(GS_ERR_ARG, "more than 65536 batches (max_samples / batch_size + 1): no round form");
+    if ((uint64_t)first_round + rounds > R)
+        return fail(GS_ERR_ARG, "first_round + rounds exceeds the settings' " + std::to_string(R) + " rounds");
+    if (state_bytes < 0 || (uint64_t)state_bytes < gs_round_layout((uint64_t)cap, R).bytes)
+        return fail(GS_ERR_ARG, "state_bytes below gs_round_state_bytes");
+    if (cap > 0 && round_seg_px((uint64_t)cap, *ss, read_knobs()) < 1)
+        return fail(GS_ERR_ARG, "one pixel's batch exceeds the partial budget");
+    return GS_OK;
+}
+
+gs_status gs_render_tiles_rounds_timed_async(const gs_device_scene* ds, const gs_camera* cam,
+                                             const gs_sample_settings* ss, uint64_t seed, const gs_partition* part,
+                                             uint32_t first_round, uint32_t rounds, void* d_state, int64_t state_bytes,
+                                             const gs_round_outputs* out, gs_counters* d_counters, void* stream,
+                                             hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters) {
+    gs_status e = check_rounds(ds, cam, ss, part, first_round, rounds, d_state, state_bytes, out, true);
+    if (e != GS_OK) return e;
+    e = ensure_placement(const_cast<gs_device_scene*>(ds), cam, ss, stream);
+    if (e != GS_OK) return e;
+    const RoundArgs ra{first_round, rounds, ss->max_samples / ss->batch_size + 1u, (uint8_t*)d_state, out->samples,
+                       out->rel_error};
+    const gs_render_outputs o{out->rgb, out->rgb8, nullptr};
+    return launch(ds, cam, ss, seed, part, &o, d_counters, stream, k_begin, k_end, nullptr, direct, zero_counters,
+                  nullptr, &ra);
+}
+
+extern "C" int64_t gs_round_state_bytes(const gs_camera* cam, const gs_partition* part, const gs_sample_settings* ss) {
+    if (!cam || !part || !ss || ss->batch_size == 0 || ss->max_samples < ss->batch_size) return -1;
+    const int64_t cap = gs_partition_capacity(cam, part);
+    const uint64_t R = (uint64_t)ss->max_samples / ss->batch_size + 1u;
+    if (cap < 0 || cap >= (int64_t)0xFFFFFFFFll || R > kMaxRounds) return -1;
+    return (int64_t)gs_round_layout((uint64_t)cap, R).bytes;
+}
+
+extern "C" gs_status gs_render_tiles_rounds_async(const gs_device_scene* ds, const gs_camera* cam,
+                                                  const gs_sample_settings* ss, uint64_t seed,
+                                                  const gs_partition* part, uint32_t first_round, uint32_t rounds,
+                                                  void* d_state, int64_t state_bytes, const gs_round_outputs* out,
+                                                  gs_counters* d_counters, void* stream) {
+    gs_status e = check_rounds(ds, cam, ss, part, first_round, rounds, d_state, state_bytes, out, false);
+    if (e != GS_OK) return e;
+    return gs_render_tiles_rounds_timed_async(ds, cam, ss, seed, part, first_round, rounds, d_state, state_bytes, out,
+                                              d_counters, stream, nullptr, nullptr, false, false);
 }
 
 int64_t gs_pass_delta_blocks(int64_t capacity) {
@@ -591,7 +682,9 @@ static gs_status grow_buffer(LaunchSlot& sl, T*& buf, size_t& have, size_t need,
 }
 
 // Sizes the slot's buffers for the launch and points the parameter block at them.
-static gs_status bind_slot(LaunchSlot& sl, hipStream_t st, const WorkPlan& w, int feat, int64_t blocks, size_t need_partial, KParams& kp) {
+// (own_rounds: the round state is the slot's; a progressive adaptive pass brings its own)
+static gs_status bind_slot(LaunchSlot& sl, hipStream_t st, const WorkPlan& w, int feat, int64_t blocks, size_t need_partial, KParams& kp,
+                           bool own_rounds = true) {
     if (w.chunk || w.n_rounds) {
         gs_status e = grow_buffer(sl, sl.partial, sl.partial_bytes, need_partial, "chunk sums");
         if (e != GS_OK) return e;
@@ -599,7 +692,7 @@ static gs_status bind_slot(LaunchSlot& sl, hipStream_t st, const WorkPlan& w, in
     }
     // batch rounds: [item-size hint, round counts][active list 0][active list 1][running sums],
     // 256-B aligned (the hint first: it outlives launches of other settings)
-    if (w.n_rounds) {
+    if (w.n_rounds && own_rounds) {
         const size_t cap = kp.capacity;
         const size_t r_counts = ((size_t)(w.n_rounds + 2) * 4 + 16 + 255) & ~(size_t)255;
         const size_t r_list = (cap * 4 + 255) & ~(size_t)255;
@@ -668,6 +761,34 @@ static gs_status enqueue_rounds(const Enqueue& q, const WorkPlan& w, const Knobs
     return GS_OK;
 }
 
+// A progressive adaptive pass: enqueue_rounds over rounds [first_round, first_round + rounds) of
+// the caller's state -- round_counts[first_round] is read on the device, so nothing here waits
+// for an earlier pass -- always in split items (whole-batch items take the stop test in the
+// megakernel, which does not write the persistent state), the fold in the combine's place;
+// then the resolve over every packed pixel.
+static gs_status enqueue_round_pass(const Enqueue& q, const WorkPlan& w, const Knobs& k, const LaunchReq& r,
+                                    const RoundArgs& ra, const KParams& kp, KParams* dP, const KArgs& a) {
+    const hipStream_t st = q.st;
+    if (ra.first_round == 0 && ra.rounds) {
+        const unsigned g_init = (unsigned)std::min<int64_t>(((int64_t)r.cap + 255) / 256, 8192);
+        HIPCHK(launch_round_init_kernel(st, g_init, dP));
+    }
+    if (q.k_begin) HIPCHK(hipEventRecord(q.k_begin, st));
+    const unsigned g_fold = (unsigned)std::min<int64_t>((w.seg_px + 255) / 256, 8192);
+    const bool rsplit = GS_USE_RSPLIT && has_rsplit(q.feat) && r.cam->max_depth > 0;
+    void (*rkern)(KArgs) = kernel_for(rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat);
+    for (uint32_t rd = ra.first_round; rd < ra.first_round + ra.rounds; rd++)
+        for (uint32_t sg = 0; sg < w.n_segs; sg++) {
+            HIPCHK(launch_round_params_kernel(st, dP, rd, sg, w.seg_px, k.sample_chunk, 0));
+            HIPCHK(launch_render_kernel(st, rkern, q.blocks, q.lds, a));
+            HIPCHK(launch_round_fold_kernel(st, g_fold, dP, rd));
+        }
+    if (q.k_end) HIPCHK(hipEventRecord(q.k_end, st));
+    HIPCHK(hipMemsetAsync(kp.round_summary, 0, GS_ROUND_SUMMARY_WORDS * 8, st));
+    HIPCHK(launch_round_resolve_kernel(st, dP, r.cap));
+    return GS_OK;
+}
+
 // One megakernel launch, then the chunk combine when the pixels' samples were split.
 static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const LaunchReq& r, const KParams* dP,
                                const KArgs& a, bool pass) {
@@ -693,7 +814,7 @@ static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const Launch
 static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                         const gs_partition* part, const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
                         hipEvent_t k_begin, hipEvent_t k_end, const VisitArgs* va, bool direct, bool zero_counters,
-                        const PassArgs* pass) {
+                        const PassArgs* pass, const RoundArgs* ra) {
     if (!ds || !cam || !ss || !part || !outs || (!outs->rgb && !outs->rgb8)) return fail(GS_ERR_ARG, "null argument");
     if (!part_ok(cam, part)) return fail(GS_ERR_ARG, "bad partition / image size");
     if (ss->batch_size == 0) return fail(GS_ERR_ARG, "batch_size 0 never terminates (camera.rs:137)");
@@ -701,6 +822,7 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     const hipStream_t st = (hipStream_t)stream;
     if (cap <= 0) {  // nothing to render; a frame context's counters still start from zero
         if (zero_counters && d_counters) HIPCHK(hipMemsetAsync(d_counters, 0, sizeof(gs_counters), st));
+        if (ra) HIPCHK(hipMemsetAsync(ra->d_state + gs_round_layout(0, ra->R).summary, 0, GS_ROUND_SUMMARY_WORDS * 8, st));
         if (k_begin) HIPCHK(hipEventRecord(k_begin, st));  // (a caller times an empty kernel span)
         if (k_end) HIPCHK(hipEventRecord(k_end, st));
         return GS_OK;
@@ -720,8 +842,16 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
 #endif
     const uint64_t lanes = (uint64_t)std::max(1, device_cus(dev)) * GS_BLOCK;
     const bool long_samples = ds->long_samples.load(std::memory_order_relaxed);
-    const WorkPlan w = pass ? plan_pass(*cam, ss->batch_size, *part, req.cap, pass->chunk, ds->feat, k, lanes, long_samples)
-                            : plan_work(*cam, *ss, *part, req.cap, ds->feat, k, lanes, long_samples, !visit_out && !va);
+    WorkPlan w = pass ? plan_pass(*cam, ss->batch_size, *part, req.cap, pass->chunk, ds->feat, k, lanes, long_samples)
+                      : plan_work(*cam, *ss, *part, req.cap, ds->feat, k, lanes, long_samples, !visit_out && !va);
+    if (ra) {  // always batch rounds, whatever gs_set_adaptive_mode and the sample chunk say (plan_work's layout)
+        w = WorkPlan{};
+        w.n_rounds = ra->R;
+        w.seg_px = (uint32_t)round_seg_px(req.cap, *ss, k);
+        if (w.seg_px < 1) return fail(GS_ERR_ARG, "one pixel's batch exceeds the partial budget");
+        w.n_segs = (uint32_t)(((uint64_t)req.cap + w.seg_px - 1) / w.seg_px);
+        w.fine_px = req.cap;
+    }
     // (under the scene's mutex from here: the placement pilot's end rewrites the records,
     // the root and the mirror prefixes under it, pilot_end)
     gs_device_scene* mds = const_cast<gs_device_scene*>(ds);
@@ -755,14 +885,29 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
                                 : w.chunk  ? (size_t)kp.n_items * 3 * sizeof(double) : 0;
     LaunchSlot& sl = mds->slots[pick_slot(mds, st, need_partial)];
     if (sl.used && sl.stream != st) HIPCHK(hipStreamWaitEvent(st, sl.done, 0));
-    gs_status e = bind_slot(sl, st, w, lc.feat, blocks, need_partial, kp);
+    gs_status e = bind_slot(sl, st, w, lc.feat, blocks, need_partial, kp, ra == nullptr);
     if (e != GS_OK) return e;
+    if (ra) {
+        const GsRoundLayout l = gs_round_layout(req.cap, ra->R);
+        if (ra->first_round == 0 && ra->rounds) HIPCHK(hipMemsetAsync(ra->d_state, 0, l.bytes, st));  // (no hint, no counts, no sums)
+        kp.rpp_hint = (unsigned long long*)(ra->d_state + l.hint);
+        kp.round_summary = (unsigned long long*)(ra->d_state + l.summary);
+        kp.round_counts = (uint32_t*)(ra->d_state + l.counts);
+        kp.active_buf[0] = (uint32_t*)(ra->d_state + l.list[0]);
+        kp.active_buf[1] = (uint32_t*)(ra->d_state + l.list[1]);
+        kp.pstate = (double*)(ra->d_state + l.pstate);
+        kp.pbatches = (uint32_t*)(ra->d_state + l.batches);
+        kp.map_samples = ra->map_samples;
+        kp.map_error = ra->map_error;
+    }
     KArgs a = fill_args(ds, lc, chunked, k);
     a.P = sl.params;
     if (outs->item_visits) HIPCHK(hipMemsetAsync(outs->item_visits, 0, (size_t)cap * sizeof(uint32_t), st));
     HIPCHK(launch_params_kernel(st, kp, sl.params));  // (zeroes the queue)
     const Enqueue q{st, (unsigned)blocks, lc.lds, lc.feat, k_begin, k_end};
-    e = w.n_rounds ? enqueue_rounds(q, w, k, req, kp, sl.params, a) : enqueue_frame(q, w, req, sl.params, a, pass != nullptr);
+    e = ra ? enqueue_round_pass(q, w, k, req, *ra, kp, sl.params, a)
+        : w.n_rounds ? enqueue_rounds(q, w, k, req, kp, sl.params, a)
+                     : enqueue_frame(q, w, req, sl.params, a, pass != nullptr);
     if (e != GS_OK) return e;
     HIPCHK(hipEventRecord(sl.done, st));
     sl.used = true;

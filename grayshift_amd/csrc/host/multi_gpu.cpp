@@ -135,6 +135,11 @@ struct Device {
     // order) and the last pass's per-block change, with its pinned host copy
     DBuf sums, delta;
     double* h_delta = nullptr;
+    // an open adaptation (gs_multi_adapt_*): the rank's round state (launch.cpp's blob), the two
+    // maps in packed order (cap u32, cap f32) and the pinned copy of the blob's summary words
+    DBuf rstate, map_samples, map_error;
+    unsigned long long* h_summary = nullptr;
+    uint64_t ad_paths = 0;  // this rank's paths so far in the adaptation's device counters
     // the frame's counters, copied back on the stream behind the frame's last work, so the
     // host's wait is the only synchronisation (a synchronous copy after it cost C1 ~25 us)
     gs_counters* h_cnt = nullptr;  // pinned
@@ -193,6 +198,19 @@ struct gs_multi {
     uint32_t acc_chunk = 0, acc_passes = 0;
     double acc_last_delta = 0.0;
     gs_counters acc_counters{};
+    // The open adaptation (gs_multi_adapt_begin .. _end): camera, settings and seed are fixed, the
+    // tile plan is the one computed at its start, and ad_rounds rounds are in the ranks' state.
+    bool ad_open = false;
+    gs_camera ad_cam{};
+    gs_sample_settings ad_ss{};
+    uint64_t ad_seed = 0, ad_active = 0, ad_samples_total = 0, ad_samples_max = 0;
+    uint32_t ad_rounds = 0, ad_R = 0;
+    // The ranks' device counters run on from pass to pass (gs_round_params_kernel sizes a round's
+    // items by the rays per path so far, as in a one-shot launch): zeroed by the first pass after
+    // _begin / _upload (ad_fresh), their sum over the ranks so far in ad_dev, and ad_counters =
+    // ad_base (an upload's) + ad_dev.
+    bool ad_fresh = true;
+    gs_counters ad_counters{}, ad_base{}, ad_dev{};
 
     ~gs_multi() {
         DeviceGuard g;
@@ -214,7 +232,11 @@ struct gs_multi {
             d.cnt.release();
             d.sums.release();
             d.delta.release();
+            d.rstate.release();
+            d.map_samples.release();
+            d.map_error.release();
             if (d.h_delta) (void)hipHostFree(d.h_delta);
+            if (d.h_summary) (void)hipHostFree(d.h_summary);
             if (d.h_cnt) (void)hipHostFree(d.h_cnt);
             if (d.scene) gs_device_scene_destroy(d.scene);
             if (d.stream) (void)hipStreamDestroy(d.stream);
@@ -238,8 +260,9 @@ struct gs_multi {
 
     gs_status partition(const gs_camera* cam, uint64_t seed, double* plan_ms);
     // pass_samples != 0: a pass of the open accumulation (cam, ss and seed are then its own)
+    // adapt: a pass of the open adaptation, of adapt_rounds rounds (0: resolve the state as it stands)
     gs_status render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, const gs_multi_outputs* out,
-                     gs_stats* stats, uint32_t pass_samples = 0);
+                     gs_stats* stats, uint32_t pass_samples = 0, bool adapt = false, uint32_t adapt_rounds = 0);
     gs_status accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk);
     void accum_end();
     // The tile (or -1) of rank `rank`'s slot `slot`, and the slots the rank holds.
@@ -247,6 +270,20 @@ struct gs_multi {
     int32_t slot_tile(int rank, int64_t slot) const;
     // Moves the sums between the ranks' packed buffers and an [H][W][3] image (to_image or back).
     gs_status permute_sums(double* image, bool to_image);
+    gs_status adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed);
+    void adapt_end();
+    // The packed pixels of rank `rank` as its launches see them (gs_partition_capacity): `cap` under
+    // a plan, fewer for the later ranks of a round-robin partition -- the size the rank's round
+    // state is laid out for.
+    int64_t rank_cap(int rank, const gs_camera& cam) const {
+        if (!order.empty()) return cap;
+        gs_partition p{rank, (int32_t)dev.size(), tw, th, nullptr, 0, 0};
+        return std::max<int64_t>(0, gs_partition_capacity(&cam, &p));
+    }
+    bool adapt_finished() const { return ad_rounds > 0 && (ad_active == 0 || ad_rounds >= ad_R); }
+    // Rank `rank`'s packed array of `elem`-byte records <-> the [H][W] image of them (to_image or
+    // back; going back, slots outside the image keep what `packed` holds).
+    void permute_rank(int rank, const gs_camera& cam, uint8_t* image, uint8_t* packed, size_t elem, bool to_image) const;
 };
 
 gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_ms) {
@@ -281,7 +318,8 @@ gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_
 }
 
 gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
-                           const gs_multi_outputs* out, gs_stats* stats, uint32_t pass_samples) {
+                           const gs_multi_outputs* out, gs_stats* stats, uint32_t pass_samples, bool adapt,
+                           uint32_t adapt_rounds) {
     if (!cam || !ss) return fail(GS_ERR_ARG, "null argument");
     if (out && !out->rgb && !out->rgb8 && !out->ppm_text) return fail(GS_ERR_ARG, "no output requested");
     if (out && out->ppm_text && !out->ppm_len) return fail(GS_ERR_ARG, "ppm_text without ppm_len");
@@ -291,6 +329,8 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
     if (acc_open && !pass_samples)  // (a new plan would invalidate the packed sums)
         return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
+    if (ad_open && !adapt)  // (likewise: the round state is in the plan's packed order)
+        return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
     DeviceGuard guard;
     const auto t0 = std::chrono::steady_clock::now();
     const int n = (int)dev.size();
@@ -333,7 +373,12 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         gs_render_outputs o{want_rgb ? (float*)(direct ? frame.p : d.packed.p) : nullptr,
                             want8 ? (uint8_t*)(direct ? frame8.p : d.packed8.p) : nullptr, nullptr};
         HIPOK(hipEventRecord(d.ev[0], d.stream));
-        if (pass_samples) {
+        if (adapt) {
+            const gs_round_outputs ro{o.rgb, o.rgb8, (uint32_t*)d.map_samples.p, (float*)d.map_error.p};
+            s = gs_render_tiles_rounds_timed_async(d.scene, cam, ss, seed, &p, ad_rounds, adapt_rounds, d.rstate.p,
+                                                   (int64_t)d.rstate.bytes, &ro, (gs_counters*)d.cnt.p, d.stream,
+                                                   d.ev[2], d.ev[3], direct, ad_fresh);
+        } else if (pass_samples) {
             HIPOK(hipMemsetAsync(d.delta.p, 0, (size_t)gs_pass_delta_blocks(cap) * 8, d.stream));
             s = gs_render_tiles_pass_timed_async(d.scene, cam, pass_samples, seed, &p, (uint32_t)acc_samples, acc_chunk,
                                                  (double*)d.sums.p, (double*)d.delta.p, &o, (gs_counters*)d.cnt.p,
@@ -423,6 +468,9 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
     for (auto& d : dev) {
         HIPOK(hipSetDevice(d.id));
         HIPOK(hipMemcpyAsync(d.h_cnt, d.cnt.p, sizeof(gs_counters), hipMemcpyDeviceToHost, d.stream));
+        if (adapt)  // (the active count the next pass's clip needs: the pass's one read-back)
+            HIPOK(hipMemcpyAsync(d.h_summary, (const char*)d.rstate.p + gs_round_layout(0, ad_R).summary,
+                                 kRoundSummaryWords * 8, hipMemcpyDeviceToHost, d.stream));
         if (pass_samples)
             HIPOK(hipMemcpyAsync(d.h_delta, d.delta.p, (size_t)gs_pass_delta_blocks(cap) * 8, hipMemcpyDeviceToHost,
                                  d.stream));
@@ -438,7 +486,9 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         float ms = 0.0f, kms = 0.0f;
         HIPOK(hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
         HIPOK(hipEventElapsedTime(&kms, d.ev[2], d.ev[3]));
-        gs_device_scene_note_frame(d.scene, (double)kms, d.h_cnt->paths);
+        const uint64_t paths_before = adapt && !ad_fresh ? d.ad_paths : 0u;  // (an adaptation's counters run on)
+        gs_device_scene_note_frame(d.scene, (double)kms, d.h_cnt->paths - paths_before);
+        d.ad_paths = d.h_cnt->paths;
         rmax = std::max(rmax, (double)ms);
         rmin = std::min(rmin, (double)ms);
         kmax = std::max(kmax, (double)kms);
@@ -473,6 +523,24 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         acc_samples += pass_samples;
         acc_passes += 1;
     }
+    if (adapt) {
+        ad_active = ad_samples_total = ad_samples_max = 0;
+        for (int i = 0; i < n; i++) {
+            ad_active += dev[i].h_summary[0];
+            ad_samples_total += dev[i].h_summary[1];
+            ad_samples_max = std::max<uint64_t>(ad_samples_max, dev[i].h_summary[2]);
+        }
+        // this pass alone: the ranks' running counters minus their sum after the last pass
+        const gs_counters before = ad_fresh ? gs_counters{} : ad_dev;
+        ad_dev = total;
+        ad_counters = ad_base;
+        add_counters(ad_counters, ad_dev);
+        const uint64_t* pb = (const uint64_t*)&before;
+        uint64_t* pt = (uint64_t*)&total;
+        for (size_t k = 0; k < sizeof(gs_counters) / sizeof(uint64_t); k++) pt[k] -= pb[k];
+        ad_fresh = false;
+        ad_rounds += adapt_rounds;
+    }
     const auto t1 = std::chrono::steady_clock::now();
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
@@ -506,6 +574,7 @@ int32_t gs_multi::slot_tile(int rank, int64_t slot) const {
 
 gs_status gs_multi::accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk) {
     if (acc_open) return fail(GS_ERR_ARG, "an accumulation is already open: gs_multi_accum_end first");
+    if (ad_open) return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
     if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
     DeviceGuard guard;
@@ -584,7 +653,238 @@ gs_status gs_multi::permute_sums(double* image, bool to_image) {
     return GS_OK;
 }
 
+// ---------------------------------------------------------------- progressive adaptation
+gs_status gs_multi::adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed) {
+    if (ad_open) return fail(GS_ERR_ARG, "an adaptation is already open: gs_multi_adapt_end first");
+    if (acc_open) return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
+    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
+    if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
+    if (ss->batch_size == 0) return fail(GS_ERR_ARG, "batch_size 0 never terminates (camera.rs:137)");
+    if (ss->max_samples < ss->batch_size)
+        return fail(GS_ERR_ARG, "the settings run one batch (max_samples < batch_size): a fixed-spp frame has its "
+                                "passes in gs_multi_accum_begin");
+    const uint64_t R = (uint64_t)ss->max_samples / ss->batch_size + 1u;
+    if (R > 65536u) return fail(GS_ERR_ARG, "more than 65536 batches (max_samples / batch_size + 1): no round form");
+    DeviceGuard guard;
+    double plan_ms = 0.0;
+    gs_status s = partition(cam, seed, &plan_ms);
+    if (s != GS_OK) return s;
+    if (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll) return fail(GS_ERR_ARG, "bad partition");
+    const GsRoundLayout l = gs_round_layout((uint64_t)cap, R);
+    for (auto& d : dev) {
+        HIPOK(hipSetDevice(d.id));
+        GROW(d.rstate, l.bytes);
+        GROW(d.map_samples, cap * 4);
+        GROW(d.map_error, cap * 4);
+        HIPOK(hipMemsetAsync(d.rstate.p, 0, l.bytes, d.stream));
+        HIPOK(hipMemsetAsync(d.map_samples.p, 0, (size_t)cap * 4, d.stream));
+        HIPOK(hipMemsetAsync(d.map_error.p, 0, (size_t)cap * 4, d.stream));
+        if (!d.h_summary &&
+            hipHostMalloc((void**)&d.h_summary, kRoundSummaryWords * 8, hipHostMallocDefault) != hipSuccess)
+            return fail(GS_ERR_OOM, "hipHostMalloc of the round summary failed");
+        HIPOK(hipStreamSynchronize(d.stream));
+    }
+    ad_cam = *cam;
+    ad_ss = *ss;
+    ad_seed = seed;
+    ad_R = (uint32_t)R;
+    ad_rounds = 0;
+    ad_active = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
+    ad_samples_total = ad_samples_max = 0;
+    ad_counters = ad_base = ad_dev = gs_counters{};
+    ad_fresh = true;
+    ad_open = true;
+    return GS_OK;
+}
+
+void gs_multi::adapt_end() {
+    DeviceGuard guard;
+    for (auto& d : dev) {
+        (void)hipSetDevice(d.id);
+        if (d.stream && !comms_broken) (void)hipStreamSynchronize(d.stream);
+        d.rstate.release();
+        d.map_samples.release();
+        d.map_error.release();
+    }
+    ad_open = false;
+}
+
+void gs_multi::permute_rank(int rank, const gs_camera& cam, uint8_t* image, uint8_t* packed, size_t elem,
+                            bool to_image) const {
+    const int64_t W = cam.image_width, H = cam.image_height, tpx = (int64_t)tw * th;
+    const int64_t tx = (W + tw - 1) / tw, nt = tx * ((H + th - 1) / th);
+    int64_t ns = cap / tpx;
+    if (order.empty()) {
+        gs_partition p{rank, (int32_t)dev.size(), tw, th, nullptr, 0, 0};
+        ns = std::min<int64_t>(ns, gs_partition_capacity(&cam, &p) / tpx);
+    }
+    for (int64_t sl = 0; sl < ns; sl++) {
+        const int64_t tile = slot_tile(rank, sl);
+        if (tile < 0 || tile >= nt) continue;
+        const int64_t x0 = (tile % tx) * tw, y0 = (tile / tx) * th;
+        const int64_t nx = std::min<int64_t>(tw, W - x0);
+        for (int64_t y = 0; y < th && y0 + y < H; y++) {
+            uint8_t* img = image + (size_t)((y0 + y) * W + x0) * elem;
+            uint8_t* pk = packed + (size_t)(sl * tpx + y * tw) * elem;
+            if (to_image)
+                std::memcpy(img, pk, (size_t)nx * elem);
+            else
+                std::memcpy(pk, img, (size_t)nx * elem);
+        }
+    }
+}
+
 extern "C" {
+
+gs_status gs_multi_adapt_begin(gs_multi* m, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed) {
+    if (!m || !cam || !ss) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    return m->adapt_begin(cam, ss, seed);
+}
+
+gs_status gs_multi_adapt_pass(gs_multi* m, uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open: gs_multi_adapt_begin first");
+    if (rounds == 0) return fail(GS_ERR_ARG, "a pass of 0 rounds");
+    const uint32_t todo = m->adapt_finished() ? 0u : std::min(rounds, m->ad_R - m->ad_rounds);
+    return m->render(&m->ad_cam, &m->ad_ss, m->ad_seed, out, stats, 0, true, todo);
+}
+
+gs_status gs_multi_adapt_info(const gs_multi* m, gs_adapt_info* info) {
+    if (!m || !info) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    std::memset(info, 0, sizeof(*info));
+    info->width = m->ad_cam.image_width;
+    info->height = m->ad_cam.image_height;
+    info->batch = m->ad_ss.batch_size;
+    info->rounds = m->ad_rounds;
+    info->max_rounds = m->ad_R;
+    info->finished = m->adapt_finished() ? 1u : 0u;
+    info->seed = m->ad_seed;
+    info->active_pixels = m->ad_active;
+    info->samples_total = m->ad_samples_total;
+    info->samples_max = m->ad_samples_max;
+    info->counters = m->ad_counters;
+    return GS_OK;
+}
+
+gs_status gs_multi_adapt_maps(gs_multi* m, uint32_t* samples, float* rel_error) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    DeviceGuard guard;
+    std::vector<uint8_t> packed((size_t)m->cap * 4);
+    for (int i = 0; i < (int)m->dev.size(); i++) {
+        Device& d = m->dev[i];
+        HIPOK(hipSetDevice(d.id));
+        HIPOK(hipStreamSynchronize(d.stream));
+        if (samples) {
+            HIPOK(hipMemcpy(packed.data(), d.map_samples.p, packed.size(), hipMemcpyDeviceToHost));
+            m->permute_rank(i, m->ad_cam, (uint8_t*)samples, packed.data(), 4, true);
+        }
+        if (rel_error) {
+            HIPOK(hipMemcpy(packed.data(), d.map_error.p, packed.size(), hipMemcpyDeviceToHost));
+            m->permute_rank(i, m->ad_cam, (uint8_t*)rel_error, packed.data(), 4, true);
+        }
+    }
+    return GS_OK;
+}
+
+gs_status gs_multi_adapt_download(gs_multi* m, double* sums, uint32_t* state) {
+    if (!m || !sums || !state) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    DeviceGuard guard;
+    std::vector<uint8_t> packed((size_t)m->cap * 40);
+    for (int i = 0; i < (int)m->dev.size(); i++) {
+        Device& d = m->dev[i];
+        const size_t rc = (size_t)m->rank_cap(i, m->ad_cam);
+        const GsRoundLayout l = gs_round_layout(rc, m->ad_R);
+        if (rc == 0) continue;
+        HIPOK(hipSetDevice(d.id));
+        HIPOK(hipStreamSynchronize(d.stream));
+        HIPOK(hipMemcpy(packed.data(), (const char*)d.rstate.p + l.pstate, rc * 40, hipMemcpyDeviceToHost));
+        m->permute_rank(i, m->ad_cam, (uint8_t*)sums, packed.data(), 40, true);
+        HIPOK(hipMemcpy(packed.data(), (const char*)d.rstate.p + l.batches, rc * 4, hipMemcpyDeviceToHost));
+        m->permute_rank(i, m->ad_cam, (uint8_t*)state, packed.data(), 4, true);
+    }
+    return GS_OK;
+}
+
+gs_status gs_multi_adapt_upload(gs_multi* m, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
+                                uint32_t rounds_done, const double* sums, const uint32_t* state,
+                                const gs_counters* counters) {
+    if (!m || !cam || !ss || !sums || !state || !counters) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    gs_status s = m->adapt_begin(cam, ss, seed);
+    if (s != GS_OK) return s;
+    auto bail = [&](gs_status st) {
+        m->adapt_end();
+        return st;
+    };
+    if (rounds_done > m->ad_R) return bail(fail(GS_ERR_ARG, "rounds_done exceeds the settings' rounds"));
+    // every pixel's word against rounds_done: an active pixel has taken every round so far, a
+    // stopped one at least one and no more than that
+    const uint64_t npx = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
+    uint64_t active = 0, total = 0, most = 0;
+    for (uint64_t k = 0; k < npx; k++) {
+        const uint32_t nb = state[k] & ~GS_ADAPT_STOPPED;
+        const bool stopped = (state[k] & GS_ADAPT_STOPPED) != 0;
+        if (stopped ? (nb < 1 || nb > rounds_done) : (nb != rounds_done || (rounds_done == m->ad_R && rounds_done)))
+            return bail(fail(GS_ERR_ARG, "a pixel's state disagrees with rounds_done"));
+        active += stopped ? 0u : 1u;
+        total += (uint64_t)nb * ss->batch_size;
+        most = std::max<uint64_t>(most, (uint64_t)nb * ss->batch_size);
+    }
+    if (rounds_done == 0) {  // (nothing to fill: the first pass initialises the state)
+        m->ad_counters = m->ad_base = *counters;
+        return GS_OK;
+    }
+    DeviceGuard guard;
+    std::vector<double> psums((size_t)m->cap * 5);
+    std::vector<uint32_t> words((size_t)m->cap), list;
+    for (int i = 0; i < (int)m->dev.size(); i++) {
+        Device& d = m->dev[i];
+        const size_t cap = (size_t)m->rank_cap(i, *cam);  // (the rank's own: its launches lay the state out for it)
+        const GsRoundLayout l = gs_round_layout(cap, m->ad_R);
+        if (cap == 0) continue;
+        std::fill(psums.begin(), psums.end(), 0.0);
+        std::fill(words.begin(), words.end(), GS_ADAPT_STOPPED);  // (padding: never active)
+        m->permute_rank(i, *cam, (uint8_t*)const_cast<double*>(sums), (uint8_t*)psums.data(), 40, false);
+        m->permute_rank(i, *cam, (uint8_t*)const_cast<uint32_t*>(state), (uint8_t*)words.data(), 4, false);
+        // the round's active list, rebuilt in packed order (its order is scheduling only)
+        list.clear();
+        for (size_t k = 0; k < cap; k++) {
+            if (!(words[k] & GS_ADAPT_STOPPED)) list.push_back((uint32_t)k);
+            if (words[k] == GS_ADAPT_STOPPED) words[k] = 0u;
+        }
+        const uint32_t n_act = (uint32_t)list.size();
+        char* blob = (char*)d.rstate.p;
+        if (hipSetDevice(d.id) != hipSuccess ||
+            hipMemcpy(blob + l.pstate, psums.data(), cap * 40, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(blob + l.batches, words.data(), cap * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            (n_act && hipMemcpy(blob + l.list[rounds_done & 1u], list.data(), (size_t)n_act * 4, hipMemcpyHostToDevice) !=
+                          hipSuccess) ||
+            hipMemcpy(blob + l.counts + (size_t)rounds_done * 4, &n_act, 4, hipMemcpyHostToDevice) != hipSuccess)
+            return bail(fail(GS_ERR_HIP, "uploading the round state failed"));
+    }
+    m->ad_rounds = rounds_done;
+    m->ad_active = active;
+    m->ad_samples_total = total;
+    m->ad_samples_max = most;
+    m->ad_counters = m->ad_base = *counters;
+    return GS_OK;
+}
+
+gs_status gs_multi_adapt_end(gs_multi* m) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    m->adapt_end();
+    return GS_OK;
+}
 
 gs_status gs_multi_accum_begin(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk) {
     if (!m || !cam) return fail(GS_ERR_ARG, "null argument");

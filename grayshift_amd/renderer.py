@@ -3,6 +3,8 @@
 * ``render(scene)`` — the one-call ``Camera::render`` replacement (linear f32 frame).
 * ``ProgressiveRenderer`` — a fixed-spp frame as a sequence of passes over device-resident
   f64 sums: preview, add samples, checkpoint, resume (bit-identical to the one-shot render).
+* ``AdaptiveRenderer`` — the scene's own adaptive SampleSettings in passes of batch rounds:
+  preview, per-pixel sample-count and error maps, checkpoint, resume (bit-identical too).
 * ``Renderer`` — device-resident scene for repeated / multi-GPU rendering: upload once,
   render this rank's tiles into a caller-provided device buffer on a given stream.
   Used by bench.py with torch tensors as the device buffers (torch is plumbing only).
@@ -192,7 +194,7 @@ class ProgressiveRenderer:
     counters of one render of n_1 + n_2 + ... samples with the same seed and chunk, bit for bit
     -- however the samples are split into passes, on any number of GPUs, and across save() /
     resume().  The scene's own SampleSettings are not used: a pass is a sample count (adaptive
-    sampling has no pass form).  chunk: the coarse sample chunk c (0 = 16); every pass is 1 to
+    settings have their own pass form, AdaptiveRenderer).  chunk: the coarse sample chunk c (0 = 16); every pass is 1 to
     64 whole chunks."""
 
     def __init__(self, scene, num_gpus=1, seed=1, chunk=0, tile=64, plan=True, devices=None, _resume=None):
@@ -357,6 +359,177 @@ class ProgressiveRenderer:
             pass
 
 
+class AdaptiveRenderer:
+    """The scene's own adaptive SampleSettings rendered in passes of batch rounds
+    (gs_multi_adapt_*): round r renders batch r of every pixel still active, and every pass
+    returns the frame resolved so far -- a stopped pixel's final colour, an active pixel's mean
+    over the samples it has taken.
+
+    The contract: whatever the split into passes, the GPU count, the tile plan or a save() /
+    resume() in between, the finished frame, its rgb8 bytes and the cumulative counters are those
+    of render() / render_multi() with the same settings and seed, bit for bit; after k rounds
+    the frame is the one-shot frame with max_samples = k * batch_size - 1."""
+
+    def __init__(self, scene, num_gpus=1, seed=1, tile=64, plan=True, devices=None, _resume=None):
+        self.scene = scene
+        self.seed = int(seed)
+        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=plan, devices=devices)
+        self._open = False
+        mr = self._mr
+        try:
+            if _resume is None:
+                N.check(N.lib.gs_multi_adapt_begin(mr.handle, C.byref(mr.cam), C.byref(mr.settings), self.seed))
+            else:
+                sums, state, meta = _resume
+                cnt = N.gs_counters(**meta["counters"])
+                N.check(N.lib.gs_multi_adapt_upload(mr.handle, C.byref(mr.cam), C.byref(mr.settings), self.seed,
+                                                    meta["rounds"], sums.ctypes.data, state.ctypes.data,
+                                                    C.byref(cnt)))
+            self._open = True
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def width(self):
+        return self._mr.width
+
+    @property
+    def height(self):
+        return self._mr.height
+
+    @property
+    def devices(self):
+        return self._mr.devices
+
+    @property
+    def info(self):
+        """gs_adapt_info: width, height, batch, rounds, max_rounds, finished, seed, active_pixels,
+        samples_total, samples_max and the cumulative counters (attributes; .as_dict())."""
+        i = N.gs_adapt_info()
+        N.check(N.lib.gs_multi_adapt_info(self._mr.handle, C.byref(i)))
+        return i
+
+    @property
+    def finished(self):
+        return bool(self.info.finished)
+
+    def render_rounds(self, n, rgb=True, rgb8=False, ppm=False):
+        """Render the next `n` rounds (clipped to what remains; none once finished) and resolve the
+        frame.  Returns a dict: the requested outputs ("rgb" [H,W,3] f32, "rgb8", "ppm"; with none
+        the f32 frame stays on the first device, frame_ptr), this pass's "counters" and "stats",
+        and "info" (info.as_dict() after the pass)."""
+        out, res, ppm_buf = _outputs(self.width, self.height, rgb, rgb8, ppm)
+        st = N.gs_stats()
+        N.check(N.lib.gs_multi_adapt_pass(self._mr.handle, int(n), C.byref(out) if out is not None else None,
+                                          C.byref(st)))
+        if ppm:
+            res["ppm"] = ppm_buf[0].raw[:ppm_buf[1].value]
+        res["counters"] = st.counters.as_dict()
+        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+        res["info"] = self.info.as_dict()
+        return res
+
+    def render_until(self, rounds=None, seconds=None, active_fraction=None, pass_rounds=1, on_pass=None):
+        """Run passes of `pass_rounds` rounds until the first bound is reached: `rounds` rounds
+        have run in all, `seconds` of wall time have passed since the call, at most
+        `active_fraction` of the pixels are still active -- or, at the latest, the frame is
+        finished.  on_pass(info, frame) is called after every pass with info.as_dict() and the
+        resolved [H,W,3] f32 frame.  Returns (info, frame) of the last pass; frame is None when no
+        pass ran.  pass_rounds: every pass ends with one resolve over the frame and one read of
+        the active count, so a larger value trades preview rate for less overhead."""
+        step = max(1, int(pass_rounds))
+        t0 = time.monotonic()
+        info, frame = self.info.as_dict(), None
+        npx = self.width * self.height
+        while not info["finished"]:
+            n = step
+            if rounds is not None:
+                n = min(n, int(rounds) - info["rounds"])
+                if n <= 0:
+                    break
+            if seconds is not None and frame is not None and time.monotonic() - t0 >= seconds:
+                break
+            res = self.render_rounds(n)
+            info, frame = res["info"], res["rgb"]
+            if on_pass is not None:
+                on_pass(info, frame)
+            if active_fraction is not None and info["active_pixels"] <= active_fraction * npx:
+                break
+        return info, frame
+
+    def sample_counts(self):
+        """[H, W] u32: the samples every pixel has taken so far (multiples of the batch size)."""
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        N.check(N.lib.gs_multi_adapt_maps(self._mr.handle, out.ctypes.data, None))
+        return out
+
+    def error_map(self):
+        """[H, W] f32: what the stop test compares with the tolerance, sqrt(confidence² · var / n)
+        / |mean| of the pixel's luminance (NaN / inf where the variance or the mean is 0/0)."""
+        out = np.zeros((self.height, self.width), dtype=np.float32)
+        N.check(N.lib.gs_multi_adapt_maps(self._mr.handle, None, out.ctypes.data))
+        return out
+
+    def state(self):
+        """(sums [H, W, 5] f64: Σr, Σg, Σb, Σlum, Σlum²; state [H, W] u32: batches taken, the top
+        bit once the pixel has stopped) in image order, copies on the host."""
+        sums = np.zeros((self.height, self.width, 5), dtype=np.float64)
+        state = np.zeros((self.height, self.width), dtype=np.uint32)
+        N.check(N.lib.gs_multi_adapt_download(self._mr.handle, sums.ctypes.data, state.ctypes.data))
+        return sums, state
+
+    @property
+    def frame_ptr(self):
+        """(device pointer of the last resolved W*H*3 f32 frame or None, its device id)."""
+        return self._mr.frame_ptr()
+
+    def save(self, path):
+        """Write a checkpoint (grayshift_amd.checkpoint, format 2): the sums and state words, the
+        rounds run, seed, settings, frame size, the gs_camera bytes and the cumulative counters."""
+        i = self.info
+        ss = self._mr.settings
+        sums, state = self.state()
+        meta = {"rounds": i.rounds, "seed": i.seed, "width": i.width, "height": i.height,
+                "confidence": ss.confidence, "tolerance": ss.tolerance, "batch_size": ss.batch_size,
+                "max_samples": ss.max_samples, "camera": bytes(self._mr.cam), "counters": i.counters.as_dict()}
+        checkpoint.write_adaptive_checkpoint(path, sums, state, meta)
+
+    @classmethod
+    def resume(cls, scene, path, **kw):
+        """Continue the checkpoint at `path` on `scene`: **kw as for the constructor (any device
+        count or tile plan).  seed defaults to the checkpoint's; the checkpoint is rejected
+        (checkpoint.CheckpointError) when its frame size, seed, SampleSettings or gs_camera bytes
+        differ from the scene's and the ones given.  Whether `scene` is otherwise the world the
+        checkpoint was rendered from is the caller's responsibility."""
+        sums, state, meta = checkpoint.read_adaptive_checkpoint(path)
+        cam = camera(scene.camera)
+        seed = kw.pop("seed", meta["seed"])
+        checkpoint.check_adaptive_compatible(meta, cam.image_width, cam.image_height, scene.settings, seed, bytes(cam))
+        return cls(scene, seed=seed, _resume=(sums, state, meta), **kw)
+
+    def close(self):
+        mr = getattr(self, "_mr", None)
+        if mr is not None:
+            if self._open and mr.handle:
+                N.lib.gs_multi_adapt_end(mr.handle)
+            self._open = False
+            mr.close()
+            self._mr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
+            pass
+
+
 def ppm_encode_async(d_rgb8, width, height, d_text, text_capacity, d_len, d_scratch, scratch_bytes, stream=0):
     """Format a device W*H*3 byte frame as the reference's PPM text on the device."""
     N.check(N.lib.gs_ppm_encode_async(C.c_void_p(d_rgb8), width, height, C.c_void_p(d_text), text_capacity,
@@ -494,6 +667,26 @@ class Renderer:
         N.check(N.lib.gs_render_tiles_pass_async(self.dev, C.byref(self.cam), samples, seed, C.byref(self.part),
                                                  sample_base, chunk, C.c_void_p(d_sums), C.byref(o),
                                                  C.c_void_p(d_counters), C.c_void_p(stream)))
+
+    def round_state_bytes(self):
+        """Bytes of the device blob render_rounds_async keeps this rank's round state in."""
+        n = N.lib.gs_round_state_bytes(C.byref(self.cam), C.byref(self.part), C.byref(self.settings))
+        if n < 0:
+            raise ValueError("the scene's settings have no round form (max_samples < batch_size?)")
+        return n
+
+    def render_rounds_async(self, first_round, rounds, d_state, state_bytes, d_rgb=0, d_rgb8=0, d_samples=0,
+                            d_rel_error=0, d_counters=0, stream=0, seed=1):
+        """One progressive adaptive pass of this rank's tiles (gs_render_tiles_rounds_async) with the
+        scene's own SampleSettings: rounds [first_round, first_round + rounds) on the round state in
+        d_state (device, round_state_bytes(); first_round 0 initialises it), then every packed
+        pixel's colour resolved into d_rgb (capacity*3 f32) and / or d_rgb8, and the maps into
+        d_samples (capacity u32) / d_rel_error (capacity f32) when given."""
+        o = N.gs_round_outputs(d_rgb or None, d_rgb8 or None, d_samples or None, d_rel_error or None)
+        N.check(N.lib.gs_render_tiles_rounds_async(self.dev, C.byref(self.cam), C.byref(self.settings), seed,
+                                                   C.byref(self.part), first_round, rounds, C.c_void_p(d_state),
+                                                   state_bytes, C.byref(o), C.c_void_p(d_counters),
+                                                   C.c_void_p(stream)))
 
     def unpack_u8_async(self, d_gathered, d_frame, world_size, stream=0):
         part = N.gs_partition(0, world_size, self.part.tile_w, self.part.tile_h, self.part.d_tile_order,

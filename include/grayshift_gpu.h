@@ -511,7 +511,8 @@ gs_status gs_debug_set_multi_same_device(int32_t on);
  * seed and chunk, bit for bit -- for any split into passes, any device count or tile plan, and
  * across a checkpoint.  That one render is gs_multi_render / gs_render at a fixed spp whose
  * coarse chunk is `chunk` (e.g. gs_set_tuning(.., sample_chunk = chunk) with spp / chunk <= 64).
- * Adaptive settings have no pass form: a pass is a sample count.
+ * Here a pass is a sample count; adaptive settings have a pass form of their own, in batch
+ * rounds ("Progressive adaptive passes" below).
  *
  * The tile-level primitive, stateless: renders samples [sample_base, sample_base + samples) of
  * this rank's packed pixels, adds them to d_sums (device, capacity*3 f64 in packed order, owned
@@ -560,6 +561,92 @@ gs_status gs_multi_accum_download(gs_multi* m, double* sums);
 gs_status gs_multi_accum_upload(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk, uint64_t samples,
                                 const double* sums, const gs_counters* counters);
 gs_status gs_multi_accum_end(gs_multi* m);
+
+/* ---- Progressive adaptive passes (additive: the ABI stays 11, no existing call changes) ----
+ * Adaptive settings (max_samples >= batch_size) in passes of batch rounds.  Write bs =
+ * batch_size and R = max_samples / bs + 1, the most batches a pixel can run.  Round r renders
+ * batch r (samples [r bs, r bs + bs)) of every pixel still active and folds it into the pixel's
+ * Σr, Σg, Σb, Σlum, Σlum² in sample order, then takes the reference's stop test.
+ *
+ * The contract:
+ *  1. Rounds rendered in passes of r_1, r_2, ... rounds until no pixel is active (at the latest
+ *     after R rounds) leave the linear f32 frame, the rgb8 bytes and the counters of gs_multi_render
+ *     / gs_render with the same settings and seed, bit for bit -- for any split into passes, any
+ *     rank count or tile plan, any gs_set_tuning sample chunk or partial budget, and across a
+ *     checkpoint.
+ *  2. After k rounds (1 <= k < R) a stopped pixel shows its final colour and an active one
+ *     Σrgb / (double)(k bs): bit for bit the one-shot frame with max_samples = k bs - 1.  The
+ *     cumulative counters equal that render's except `pixels`, which counts the stopped pixels.
+ *  3. The maps, per pixel: `samples` (u32) the samples taken so far, a multiple of bs;
+ *     `rel_error` (f32) what the stop test compares with `tolerance`, computed in f64, in this
+ *     order and without contraction, from the pixel's stored sums and n = its samples:
+ *       mean = lsum / n;  var = 1.0 / (n - 1.0) * (lsq - lsum * lsum / n);
+ *       rel_error = sqrt(confidence * confidence * var / n / (mean * mean))
+ *     A stopped pixel keeps its final sums.  NaN and inf are legal values (batch size 1 gives
+ *     0/0 after the first round; a black pixel has mean 0).
+ *  4. The state crosses to the host in image order: `sums` [H][W][5] f64 (Σr, Σg, Σb, Σlum, Σlum²)
+ *     and `state` [H][W] u32 (batches taken; the top bit once the pixel has stopped), and an
+ *     upload of these continues to the same bits on any rank count.
+ *
+ * The tile-level primitive, stateless: renders rounds [first_round, first_round + rounds) of this
+ * rank's packed pixels on the state in d_state, a caller-owned device blob of at least
+ * gs_round_state_bytes(cam, part, ss) bytes (-1: bad arguments, or settings with no round form)
+ * whose layout is private; first_round == 0 initialises it.  Then every packed pixel's colour is
+ * resolved into out->rgb / out->rgb8 (at least one non-NULL; padding pixels get 0) -- stopped
+ * pixels too, so a buffer never seen before is filled whole -- and the maps into out->samples /
+ * out->rel_error when non-NULL, all indexed per packed pixel.  Round items are always split
+ * (gs_debug_set_round_items is ignored).  GS_ERR_ARG, before any device work, when: an
+ * argument is NULL (d_counters may be), the partition is bad, rounds == 0, batch_size == 0, the
+ * settings run one batch (max_samples < batch_size: see gs_render_tiles_pass_async), R > 65536,
+ * first_round + rounds > R, state_bytes is too small, or one pixel's batch (batch_size * 24
+ * bytes) exceeds the partial budget.  d_counters is accumulated into; `pixels` counts stops. */
+#define GS_ADAPT_STOPPED 0x80000000u /* a `state` word's top bit: the pixel has stopped */
+typedef struct gs_round_outputs {
+    float* rgb;        /* capacity*3 f32, linear (nullable when rgb8 is set) */
+    uint8_t* rgb8;     /* capacity*3 u8, write_color bytes (nullable) */
+    uint32_t* samples; /* capacity u32 (nullable) */
+    float* rel_error;  /* capacity f32 (nullable) */
+} gs_round_outputs;
+int64_t gs_round_state_bytes(const gs_camera* cam, const gs_partition* part, const gs_sample_settings* ss);
+gs_status gs_render_tiles_rounds_async(const gs_device_scene* scene, const gs_camera* cam,
+                                       const gs_sample_settings* ss, uint64_t seed, const gs_partition* part,
+                                       uint32_t first_round, uint32_t rounds, void* d_state, int64_t state_bytes,
+                                       const gs_round_outputs* out, gs_counters* d_counters, void* stream);
+
+/* The frame context's adaptation.  gs_multi_adapt_begin fixes the camera, the settings and the
+ * seed, computes the tile plan once and allocates the round state on every rank.  Each
+ * gs_multi_adapt_pass renders the next `rounds` rounds (clipped to what remains) on every rank
+ * and delivers the resolved frame like gs_multi_accum_pass; once the adaptation is finished (no
+ * pixel active) a pass renders nothing and delivers the same frame again.  While an adaptation
+ * is open gs_multi_render and gs_multi_accum_begin return GS_ERR_ARG, and gs_multi_adapt_begin
+ * does while an accumulation is open; calls without an open adaptation return GS_ERR_ARG.
+ * gs_multi_adapt_end closes it and frees the state (gs_multi_destroy does too). */
+typedef struct gs_adapt_info {
+    int32_t width, height;
+    uint32_t batch;          /* batch_size */
+    uint32_t rounds;         /* rounds run so far */
+    uint32_t max_rounds;     /* R */
+    uint32_t finished;       /* 1: no pixel is active */
+    uint64_t seed;
+    uint64_t active_pixels;
+    uint64_t samples_total;  /* Σ over pixels of the samples taken: equals counters.paths */
+    uint64_t samples_max;    /* the most samples any pixel has taken */
+    gs_counters counters;    /* cumulative; `pixels` counts the stopped pixels */
+} gs_adapt_info;
+gs_status gs_multi_adapt_begin(gs_multi* m, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed);
+gs_status gs_multi_adapt_pass(gs_multi* m, uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats);
+gs_status gs_multi_adapt_info(const gs_multi* m, gs_adapt_info* info);
+/* The maps of contract item 3 as host arrays in image order, [H][W] each; either may be NULL.
+ * Before the first pass every value is 0.  Not hot: the tile permutation runs on the host. */
+gs_status gs_multi_adapt_maps(gs_multi* m, uint32_t* samples, float* rel_error);
+/* Checkpoints (contract item 4).  gs_multi_adapt_upload opens an adaptation like _begin and fills
+ * it: `rounds_done` rounds are in `sums` / `state`, `counters` are the cumulative counters saved
+ * with them.  GS_ERR_ARG when a pixel's state disagrees with rounds_done. */
+gs_status gs_multi_adapt_download(gs_multi* m, double* sums, uint32_t* state);
+gs_status gs_multi_adapt_upload(gs_multi* m, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
+                                uint32_t rounds_done, const double* sums, const uint32_t* state,
+                                const gs_counters* counters);
+gs_status gs_multi_adapt_end(gs_multi* m);
 
 /* Path of the RCCL library gs_render_multi uses (loaded on this call), or NULL. */
 const char* gs_rccl_library(void);
