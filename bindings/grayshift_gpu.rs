@@ -142,6 +142,12 @@ pub struct gs_round_outputs {
     pub rgb: *mut f32, pub rgb8: *mut u8, pub samples: *mut u32, pub rel_error: *mut f32,
 }
 
+/// One camera of a views call and its seed (additive, ABI 11).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_view {
+    pub cam: gs_camera, pub seed: u64,
+}
+
 /// An open adaptation of the frame context (progressive adaptive passes; additive, ABI 11).
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct gs_adapt_info {
@@ -272,6 +278,15 @@ extern "C" {
                                  rounds_done: u32, sums: *const f64, state: *const u32,
                                  counters: *const gs_counters) -> gs_status;
     pub fn gs_multi_adapt_end(m: *mut gs_multi) -> gs_status;
+    /// Views: V cameras of one scene (one width and height) in a single launch; view v's frames
+    /// are the bits of a fixed-spp render of its camera with its seed and the same chunk.
+    pub fn gs_render_tiles_views_async(scene: *const gs_device_scene, views: *const gs_view, n_views: u32,
+                                       samples: u32, chunk: u32, part: *const gs_partition,
+                                       out: *const gs_render_outputs, d_counters: *mut gs_counters,
+                                       stream: *mut c_void) -> gs_status;
+    pub fn gs_multi_render_views(m: *mut gs_multi, views: *const gs_view, n_views: u32, samples: u32, chunk: u32,
+                                 out: *const gs_multi_outputs, stats: *mut gs_stats) -> gs_status;
+    pub fn gs_views_chunk(scene: *const gs_device_scene, cam: *const gs_camera, samples: u32) -> u32;
 }
 
 pub fn last_error() -> String {

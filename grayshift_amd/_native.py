@@ -182,6 +182,10 @@ class gs_adapt_info(C.Structure):
         return d
 
 
+class gs_view(C.Structure):
+    _fields_ = [("cam", gs_camera), ("seed", C.c_uint64)]
+
+
 # Every symbol include/*.h declares, with its ctypes signature.
 _P = C.c_void_p
 SIGNATURES = {
@@ -263,6 +267,11 @@ SIGNATURES = {
     "gs_multi_adapt_upload": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,
                                           C.c_uint32, _P, _P, C.POINTER(gs_counters)]),
     "gs_multi_adapt_end": (C.c_int32, [_P]),
+    "gs_render_tiles_views_async": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(gs_partition), C.POINTER(gs_render_outputs), _P, _P]),
+    "gs_multi_render_views": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.POINTER(gs_multi_outputs), C.POINTER(gs_stats)]),
+    "gs_views_chunk": (C.c_uint32, [_P, C.POINTER(gs_camera), C.c_uint32]),
     # grayshift_host.h
     "gs_host_scene_from_spec": (C.c_int32, [C.POINTER(gs_scene_spec), C.POINTER(_P)]),
     "gs_host_scene_destroy": (C.c_int32, [_P]),

@@ -58,6 +58,9 @@
                              // chunk != 0, max_depth > 0) -- the fixed kernel's sample loop, its items
                              // taken from the round's active list and each sample's colour written for
                              // the combine; no stop test, Σlum or batch end in the kernel (round 6)
+#define GS_FEAT_VIEWS 2048   // with GS_FEAT_FIXED: a batch of cameras as one tall frame (KParams.views; the views
+                             // calls, gs_render_tiles_views_async): the camera-ray step takes its camera, seed
+                             // and max_depth from the record of the view the pixel lies in
 #ifndef GS_NODE_STEPS
 #define GS_NODE_STEPS 8  // node steps per unrolled node pass (the render kernel, below)
 #endif
@@ -284,8 +287,25 @@ struct KParams {
     uint32_t* map_samples;    // per packed pixel: samples taken so far (nullable)
     float* map_error;         // per packed pixel: the stop test's relative error (nullable)
     unsigned long long* round_summary;  // [GS_ROUND_SUMMARY_WORDS]: active pixels, Σ samples, max samples, 0
+    // Views (gs_render_tiles_views_async; DESIGN.md §3.2 "Views"): the launch's frame is V views
+    // of W x H stacked into W x (V H), view v in rows [v H, (v + 1) H) -- `cam` holds that tall
+    // frame's size (the packed-pixel validity test, the output index) and the tiles, chunks,
+    // sums and combine run on it unchanged.  A GS_FEAT_VIEWS kernel's camera-ray step reads
+    // views[pixel / (W H)] for the camera, the seed and max_depth, and seeds the stream with
+    // the pixel's index inside its view.  Every other launch leaves these null / zero.
+    const gs_view* views;  // [V] (device)
+    UDiv u_vpx;            // W H, the pixels of one view
 };
 #define GS_ROUND_SUMMARY_WORDS 4
+
+// gs_views_kernel's argument: up to GS_VIEW_BATCH of a views launch's records by value (a
+// kernel's arguments hold 4 KiB), written to views[first, first + n) of the slot's array.
+#define GS_VIEW_BATCH 16
+struct ViewBatch {
+    gs_view v[GS_VIEW_BATCH];
+    uint32_t first, n;
+};
+static_assert(sizeof(gs_view) % 8 == 0 && sizeof(ViewBatch) <= 3072, "gs_views_kernel copies 8-byte words of a small argument");
 
 // gs_accumulate_kernel's grid: one block of 256 per 256 packed pixels up to 2048 blocks (a
 // grid-stride loop past that) -- a function of the capacity alone, so the per-block partial

@@ -8,9 +8,13 @@
 void (*kernel_for(int feat))(KArgs);
 // A split batch round may take the (feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT) instantiation.
 bool has_rsplit(int feat);
+// A views launch may take the (feat | GS_FEAT_FIXED | GS_FEAT_VIEWS) instantiation (for such a
+// feature set kernel_for returns null when there is none: a views launch has no fallback).
+bool has_views(int feat);
 
 // Each enqueues one kernel on `st` and returns that launch's error (hipGetLastError()).
 hipError_t launch_params_kernel(hipStream_t st, const KParams& kp, KParams* dst);  // (zeroes the queue)
+hipError_t launch_views_kernel(hipStream_t st, const ViewBatch& vb, gs_view* dst);  // (vb.n records to dst + vb.first)
 hipError_t launch_combine_kernel(hipStream_t st, unsigned grid, const KParams* P);
 // (a progressive pass's combine; its grid is gs_accum_blocks(capacity), the size of KParams::delta)
 hipError_t launch_accumulate_kernel(hipStream_t st, const KParams* P, uint32_t capacity);

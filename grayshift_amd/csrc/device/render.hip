@@ -1188,6 +1188,8 @@ __global__ __launch_bounds__(GS_BLOCK, GS_MIN_WAVES) void gs_render_kernel(KArgs
     // ... or a batch round's split items in that form (GS_FEAT_RSPLIT: per-sample colours)
     constexpr bool kRsplit = kFixed && (FEAT & GS_FEAT_RSPLIT) != 0;
     constexpr bool kGeneral = (FEAT & GS_FEAT_GENERAL) != 0;
+    // ... or of a batch of cameras stacked into one tall frame (GS_FEAT_VIEWS: KParams.views)
+    constexpr bool kViews = kFixed && (FEAT & GS_FEAT_VIEWS) != 0;
     // (t_in_lds kernels: the throughput's three fields first, at fixed offsets)
 #define LD(k) s_d[((k) + (t_in_lds(FEAT) ? 3 : 0)) * GS_BLOCK + tid]
 #define LI(k) s_i[(k) * GS_BLOCK + tid]
@@ -1372,8 +1374,20 @@ __global__ __launch_bounds__(GS_BLOCK, GS_MIN_WAVES) void gs_render_kernel(KArgs
             }
             // Camera::get_ray (camera.rs:204-221) on the seeded stream of this sample
             const uint32_t pix = LI(L_PIX);
-            const uint32_t pj = udiv(pix, P->u_w), pi = pix - pj * (uint32_t)cam.image_width;
-            rng = stream_seed(P->seed, pix, LI(L_SAMPLE));
+            // (a views launch: the pixel of the tall frame lies in view pix / (W H); its index,
+            // column and row there, that view's camera and seed -- lanes of a wave may differ)
+            uint32_t vpix = pix;
+            const gs_camera* vcam = &cam;
+            uint64_t vseed = 0;
+            if constexpr (kViews) {
+                const uint32_t view = udiv(pix, P->u_vpx);
+                vpix = pix - view * P->u_vpx.d;
+                vcam = &P->views[view].cam;
+                vseed = P->views[view].seed;
+            }
+            const gs_camera& cam = *vcam;  // (image_width: the same in every view and the tall frame)
+            const uint32_t pj = udiv(vpix, P->u_w), pi = vpix - pj * (uint32_t)cam.image_width;
+            rng = stream_seed(kViews ? vseed : P->seed, vpix, LI(L_SAMPLE));
             atomicAdd(&s_cnt[C_PATHS], 1ull);
             double offx = wy_f64(rng) - 0.5;
             double offy = wy_f64(rng) - 0.5;
@@ -2271,6 +2285,15 @@ __global__ void gs_params_kernel(KParams kp, KParams* __restrict__ dst) {
     if (kp.zero_counters && blockIdx.x == 0 && threadIdx.x < sizeof(gs_counters) / 8) kp.counters[threadIdx.x] = 0ull;
 }
 
+// A views launch's records reach the slot's array the same way, GS_VIEW_BATCH per launch: one
+// 8-byte word per thread (sizeof(gs_view) is a multiple of 8).
+__global__ void gs_views_kernel(ViewBatch vb, gs_view* __restrict__ dst) {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(vb.v);
+    uint64_t* out = reinterpret_cast<uint64_t*>(dst + vb.first);
+    const uint32_t words = vb.n * (uint32_t)(sizeof(gs_view) / 8);
+    for (uint32_t k = threadIdx.x; k < words; k += blockDim.x) out[k] = src[k];
+}
+
 // Chunked single-batch renders: a pixel's colour is the sum of its chunks' Σrgb, taken
 // in chunk (= sample) order, over the batch size (camera.rs:142-160 with one batch).
 // Padding slots of partial tiles get zeros.
@@ -2793,12 +2816,16 @@ void (*kernel_for(int feat))(KArgs) {
     (void)feat;
     return gs_render_kernel<GS_ONLY_FEAT>;
 #else
-    // The product instantiations, each also in its fixed-spp form (| GS_FEAT_FIXED); those
-    // without media or BVHs under instances also in the split batch-round form (| GS_FEAT_FIXED
-    // | GS_FEAT_RSPLIT; has_rsplit).
-#define GS_K(F)                                              \
+    // The product instantiations, each also in its fixed-spp form (| GS_FEAT_FIXED) and in the
+    // views form of that (| GS_FEAT_FIXED | GS_FEAT_VIEWS; has_views); those without media or BVHs
+    // under instances also in the split batch-round form (| GS_FEAT_FIXED | GS_FEAT_RSPLIT;
+    // has_rsplit).  The catch-all kernel (GS_K0) has no views form.
+#define GS_K0(F)                                             \
     case (F): return gs_render_kernel<(F)>;                  \
     case (F) | GS_FEAT_FIXED: return gs_render_kernel<(F) | GS_FEAT_FIXED>;
+#define GS_K(F) \
+    GS_K0(F)    \
+    case (F) | GS_FEAT_FIXED | GS_FEAT_VIEWS: return gs_render_kernel<(F) | GS_FEAT_FIXED | GS_FEAT_VIEWS>;
 #define GS_KR(F) \
     GS_K(F)      \
     case (F) | GS_FEAT_FIXED | GS_FEAT_RSPLIT: return gs_render_kernel<(F) | GS_FEAT_FIXED | GS_FEAT_RSPLIT>;
@@ -2822,7 +2849,7 @@ void (*kernel_for(int feat))(KArgs) {
         GS_KR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN | GS_FEAT_MIXED | GS_FEAT_LDSTREE)
         GS_KR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN | GS_FEAT_MIXED | GS_FEAT_PLAIN)
         GS_KR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN | GS_FEAT_MIXED | GS_FEAT_PLAIN | GS_FEAT_LDSTREE)
-        GS_K(GS_FEAT_GENERAL_KERNEL)
+        GS_K0(GS_FEAT_GENERAL_KERNEL)
         GS_KR(GS_FEAT_SPHLEAF)
         GS_KR(GS_FEAT_SPHLEAF | GS_FEAT_LDSTREE)
         GS_KR(GS_FEAT_SPHLEAF | GS_FEAT_MIXED)
@@ -2830,10 +2857,13 @@ void (*kernel_for(int feat))(KArgs) {
         GS_KR(GS_FEAT_SPHLEAF | GS_FEAT_MIXED | GS_FEAT_PLAIN)
         GS_KR(GS_FEAT_SPHLEAF | GS_FEAT_MIXED | GS_FEAT_PLAIN | GS_FEAT_LDSTREE)
         case GS_FEAT_FIXED: return gs_render_kernel<GS_FEAT_FIXED>;
+        case GS_FEAT_FIXED | GS_FEAT_VIEWS: return gs_render_kernel<GS_FEAT_FIXED | GS_FEAT_VIEWS>;
         case GS_FEAT_FIXED | GS_FEAT_RSPLIT: return gs_render_kernel<GS_FEAT_FIXED | GS_FEAT_RSPLIT>;
         case GS_FEAT_PILOT: return gs_render_kernel<GS_FEAT_PILOT>;
-        default: return gs_render_kernel<0>;
+        // (a views launch never falls back to a kernel that ignores KParams.views)
+        default: return (feat & GS_FEAT_VIEWS) ? nullptr : gs_render_kernel<0>;
     }
+#undef GS_K0
 #undef GS_KR
 #undef GS_K
 #endif
@@ -2846,6 +2876,23 @@ bool has_rsplit(int feat) {
 #else
     return (feat & (GS_FEAT_MEDIA | GS_FEAT_NESTED | GS_FEAT_GENERAL | GS_FEAT_VISITS)) == 0;
 #endif
+}
+
+// A views launch has its (F | FIXED | VIEWS) instantiation (kernel_for's GS_K list): every
+// product kernel but the catch-all one and the pilot's.
+bool has_views(int feat) {
+#ifdef GS_ONLY_FEAT
+    (void)feat;
+    return false;
+#else
+    return (feat & (GS_FEAT_GENERAL | GS_FEAT_VISITS)) == 0 && kernel_for(feat | GS_FEAT_FIXED | GS_FEAT_VIEWS) != nullptr;
+#endif
+}
+// The views of a views launch, at most GS_VIEW_BATCH per call: by value, like gs_params_kernel's
+// block, so the caller's array is read before the call returns.
+hipError_t launch_views_kernel(hipStream_t st, const ViewBatch& vb, gs_view* dst) {
+    hipLaunchKernelGGL(gs_views_kernel, dim3(1), dim3(64), 0, st, vb, dst);
+    return hipGetLastError();
 }
 
 // Each launcher enqueues one kernel on the stream and returns that launch's error.

@@ -29,6 +29,18 @@ gs_status gs_render_tiles_pass_timed_async(const gs_device_scene* ds, const gs_c
                                            hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters);
 int64_t gs_pass_delta_blocks(int64_t capacity);
 
+// gs_render_tiles_views_async with the same extras (direct: outs are the [V][H][W][3] frames).
+gs_status gs_render_tiles_views_timed_async(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                            uint32_t samples, uint32_t chunk, const gs_partition* part,
+                                            const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
+                                            hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters);
+// The checks of a views call that need no partition (all on the arguments alone), and the tall
+// frame's camera: view 0's with image_height = V H.  c: the chunk, resolved (never 0).
+gs_status gs_views_check(const gs_device_scene* ds, const gs_view* views, uint32_t n_views, uint32_t samples, uint32_t c,
+                         gs_camera* tall);
+// ... and those of one rank's share of the tall frame, `cap` packed pixels (gs_partition_capacity).
+gs_status gs_views_check_cap(int64_t cap, uint32_t samples, uint32_t c);
+
 // gs_render_tiles_rounds_async with the same extras.  rounds == 0 (this form only) renders
 // nothing and resolves the state as it stands.  After the call's work the blob's summary words
 // (GsRoundLayout::summary) hold this rank's active pixels, Σ samples and max samples of a pixel.

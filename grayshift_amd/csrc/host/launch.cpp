@@ -227,10 +227,17 @@ struct RoundArgs {
     uint32_t* map_samples;
     float* map_error;
 };
+// A views launch (gs_render_tiles_views_async): `cam` is the tall frame's camera, the camera-ray
+// step reads `views` (host; uploaded to the slot by the launch), the coarse chunk as given.
+struct ViewsArgs {
+    const gs_view* views;
+    uint32_t n, chunk;
+};
 static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                         const gs_partition* part, const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
                         hipEvent_t k_begin, hipEvent_t k_end, const VisitArgs* va, bool direct = false,
-                        bool zero_counters = false, const PassArgs* pass = nullptr, const RoundArgs* ra = nullptr);
+                        bool zero_counters = false, const PassArgs* pass = nullptr, const RoundArgs* ra = nullptr,
+                        const ViewsArgs* vw = nullptr);
 static gs_status ensure_placement(gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss,
                                   void* stream);
 
@@ -282,6 +289,73 @@ extern "C" gs_status gs_render_tiles_pass_async(const gs_device_scene* ds, const
                                                 gs_counters* d_counters, void* stream) {
     return gs_render_tiles_pass_timed_async(ds, cam, samples, seed, part, sample_base, chunk, d_sums, nullptr, outs,
                                             d_counters, stream, nullptr, nullptr, false, false);
+}
+
+// ---------------------------------------------------------------- views
+// The checks of a views call that need no partition, all on the arguments alone: nothing here
+// reads the scene or touches a device.
+gs_status gs_views_check(const gs_device_scene* ds, const gs_view* views, uint32_t n_views, uint32_t samples, uint32_t c,
+                         gs_camera* tall) {
+    if (!ds || !views || !tall) return fail(GS_ERR_ARG, "null argument");
+    if (n_views == 0) return fail(GS_ERR_ARG, "a views call of 0 views");
+    const gs_camera& c0 = views[0].cam;
+    if (c0.image_width <= 0 || c0.image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
+    for (uint32_t v = 0; v < n_views; v++) {
+        if (views[v].cam.image_width != c0.image_width || views[v].cam.image_height != c0.image_height)
+            return fail(GS_ERR_ARG, "view " + std::to_string(v) + " differs from view 0 in width or height");
+        if (views[v].cam.max_depth == 0) return fail(GS_ERR_ARG, "view " + std::to_string(v) + " has max_depth 0");
+    }
+    if (samples == 0) return fail(GS_ERR_ARG, "a views call of 0 samples");
+    if (samples % c != 0) return fail(GS_ERR_ARG, "samples is not a multiple of the chunk");
+    if (samples / c > 64u) return fail(GS_ERR_ARG, "more than 64 chunks per pixel");
+    // (the tall frame's pixel ids are u32, its height an i32)
+    if ((uint64_t)n_views * (uint64_t)c0.image_width * (uint64_t)c0.image_height >= 0xFFFFFFFFull ||
+        (uint64_t)n_views * (uint64_t)c0.image_height > 0x7FFFFFFFull)
+        return fail(GS_ERR_ARG, "views x width x height does not fit 32-bit pixel ids");
+    *tall = c0;
+    tall->image_height = (int32_t)(n_views * (uint32_t)c0.image_height);
+    return GS_OK;
+}
+
+// ... and those of one rank's share of the tall frame, `cap` packed pixels.
+gs_status gs_views_check_cap(int64_t cap, uint32_t samples, uint32_t c) {
+    if (cap < 0) return fail(GS_ERR_ARG, "bad partition / image size");
+    if ((uint64_t)cap * (samples / c) >= 0xFFFFFFFFull) return fail(GS_ERR_ARG, "too many work items for the 32-bit work queue");
+    if ((uint64_t)cap * (samples / c) * 24u > read_knobs().partial_budget)
+        return fail(GS_ERR_ARG, "the views' chunk sums exceed the partial budget: fewer views per call");
+    return GS_OK;
+}
+static gs_status check_views_part(const gs_camera& tall, const gs_partition* part, uint32_t samples, uint32_t c,
+                                  const gs_render_outputs* outs) {
+    if (!part || !outs || (!outs->rgb && !outs->rgb8)) return fail(GS_ERR_ARG, "null argument");
+    if (outs->item_visits) return fail(GS_ERR_ARG, "a views call has no per-pixel visit output");
+    return gs_views_check_cap(gs_partition_capacity(&tall, part), samples, c);
+}
+
+gs_status gs_render_tiles_views_timed_async(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                            uint32_t samples, uint32_t chunk, const gs_partition* part,
+                                            const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
+                                            hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters) {
+    const uint32_t c = chunk ? chunk : 16u;
+    gs_camera tall;
+    gs_status e = gs_views_check(ds, views, n_views, samples, c, &tall);
+    if (e == GS_OK) e = check_views_part(tall, part, samples, c, outs);
+    if (e != GS_OK) return e;
+    if (!has_views(ds->feat))
+        return fail(GS_ERR_UNSUPPORTED, "the scene needs the catch-all kernel, which has no views form");
+    const gs_sample_settings ss{0.0, 0.0, samples, 0};  // one batch of `samples` (max_samples < batch_size)
+    e = ensure_placement(const_cast<gs_device_scene*>(ds), &views[0].cam, &ss, stream);  // (view 0's own frame)
+    if (e != GS_OK) return e;
+    const ViewsArgs vw{views, n_views, c};
+    return launch(ds, &tall, &ss, 0, part, outs, d_counters, stream, k_begin, k_end, nullptr, direct, zero_counters,
+                  nullptr, nullptr, &vw);
+}
+
+extern "C" gs_status gs_render_tiles_views_async(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                                 uint32_t samples, uint32_t chunk, const gs_partition* part,
+                                                 const gs_render_outputs* outs, gs_counters* d_counters, void* stream) {
+    return gs_render_tiles_views_timed_async(ds, views, n_views, samples, chunk, part, outs, d_counters, stream, nullptr,
+                                             nullptr, false, false);
 }
 
 // ---------------------------------------------------------------- progressive adaptive passes
@@ -513,6 +587,21 @@ static WorkPlan plan_pass(const gs_camera& cam, uint32_t bs, const gs_partition&
     if ((uint64_t)w.fine_px * w.cpp + ((uint64_t)cap - w.fine_px) * w.fine_cpp >= 0xFFFFFFFFull)
         w.fine_px = cap, w.fine_chunk = 1, w.fine_cpp = 1;
     return w;
+}
+
+// The coarse chunk of a one-shot fixed-spp render of `cam`'s own frame: plan_work's, with a
+// render that leaves its pixels whole (c >= samples, or the never-split knob) as one chunk.
+extern "C" uint32_t gs_views_chunk(const gs_device_scene* ds, const gs_camera* cam, uint32_t samples) {
+    if (!cam || samples == 0 || cam->image_width <= 0 || cam->image_height <= 0) {
+        (void)fail(GS_ERR_ARG, "bad argument");
+        return 0;
+    }
+    const Knobs k = read_knobs();
+    if (k.sample_chunk == 0) return samples;
+    const gs_sample_settings ss{0.0, 0.0, samples, 0};
+    const uint64_t frame_px = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
+    // (no scene: the rule for one whose samples are alike -- no media, BVHs under instances or staged shading)
+    return std::min(coarse_chunk(frame_px, ss, ds ? ds->feat : 0, k).c, samples);
 }
 
 // ---------------------------------------------------------------- the launch shape
@@ -791,13 +880,16 @@ static gs_status enqueue_round_pass(const Enqueue& q, const WorkPlan& w, const K
 
 // One megakernel launch, then the chunk combine when the pixels' samples were split.
 static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const LaunchReq& r, const KParams* dP,
-                               const KArgs& a, bool pass) {
+                               const KArgs& a, bool pass, bool views) {
     if (q.k_begin) HIPCHK(hipEventRecord(q.k_begin, q.st));
     const bool pilot_kernel = r.va != nullptr;
     // (a fixed-spp chunked launch takes the instantiation without the adaptive paths)
     const bool fixed = GS_USE_FIXED && w.chunk != 0 && !w.n_rounds && r.cam->max_depth > 0;
-    HIPCHK(launch_render_kernel(q.st, kernel_for(pilot_kernel ? GS_FEAT_PILOT : q.feat | (fixed ? GS_FEAT_FIXED : 0)),
-                                q.blocks, q.lds, a));
+    // (a views launch: always chunked, every view's max_depth > 0 -- the fixed kernel's views form)
+    const int feat = views         ? q.feat | GS_FEAT_FIXED | GS_FEAT_VIEWS
+                     : pilot_kernel ? GS_FEAT_PILOT
+                                    : q.feat | (fixed ? GS_FEAT_FIXED : 0);
+    HIPCHK(launch_render_kernel(q.st, kernel_for(feat), q.blocks, q.lds, a));
     if (q.k_end) HIPCHK(hipEventRecord(q.k_end, q.st));
     if (pass) {  // (always chunked: the pass's sums join the frame's)
         HIPCHK(launch_accumulate_kernel(q.st, dP, r.cap));
@@ -814,7 +906,7 @@ static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const Launch
 static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                         const gs_partition* part, const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
                         hipEvent_t k_begin, hipEvent_t k_end, const VisitArgs* va, bool direct, bool zero_counters,
-                        const PassArgs* pass, const RoundArgs* ra) {
+                        const PassArgs* pass, const RoundArgs* ra, const ViewsArgs* vw) {
     if (!ds || !cam || !ss || !part || !outs || (!outs->rgb && !outs->rgb8)) return fail(GS_ERR_ARG, "null argument");
     if (!part_ok(cam, part)) return fail(GS_ERR_ARG, "bad partition / image size");
     if (ss->batch_size == 0) return fail(GS_ERR_ARG, "batch_size 0 never terminates (camera.rs:137)");
@@ -842,7 +934,9 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
 #endif
     const uint64_t lanes = (uint64_t)std::max(1, device_cus(dev)) * GS_BLOCK;
     const bool long_samples = ds->long_samples.load(std::memory_order_relaxed);
-    WorkPlan w = pass ? plan_pass(*cam, ss->batch_size, *part, req.cap, pass->chunk, ds->feat, k, lanes, long_samples)
+    // (a views launch: a pass's plan on the tall frame -- always chunked, the chunk as given)
+    WorkPlan w = pass || vw ? plan_pass(*cam, ss->batch_size, *part, req.cap, pass ? pass->chunk : vw->chunk, ds->feat, k,
+                                        lanes, long_samples)
                       : plan_work(*cam, *ss, *part, req.cap, ds->feat, k, lanes, long_samples, !visit_out && !va);
     if (ra) {  // always batch rounds, whatever gs_set_adaptive_mode and the sample chunk say (plan_work's layout)
         w = WorkPlan{};
@@ -900,6 +994,20 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
         kp.map_samples = ra->map_samples;
         kp.map_error = ra->map_error;
     }
+    if (vw) {  // the views' records into the slot's array, behind the slot's previous launch on the stream
+        if (!has_views(lc.feat)) return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's kernel");
+        e = grow_buffer(sl, sl.views, sl.views_bytes, (size_t)vw->n * sizeof(gs_view), "views");
+        if (e != GS_OK) return e;
+        for (uint32_t first = 0; first < vw->n; first += GS_VIEW_BATCH) {
+            ViewBatch vb{};
+            vb.first = first;
+            vb.n = std::min<uint32_t>(GS_VIEW_BATCH, vw->n - first);
+            std::memcpy(vb.v, vw->views + first, (size_t)vb.n * sizeof(gs_view));
+            HIPCHK(launch_views_kernel(st, vb, sl.views));
+        }
+        kp.views = sl.views;
+        kp.u_vpx = gsd::udiv_make((uint32_t)cam->image_width * (uint32_t)vw->views[0].cam.image_height);
+    }
     KArgs a = fill_args(ds, lc, chunked, k);
     a.P = sl.params;
     if (outs->item_visits) HIPCHK(hipMemsetAsync(outs->item_visits, 0, (size_t)cap * sizeof(uint32_t), st));
@@ -907,7 +1015,7 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     const Enqueue q{st, (unsigned)blocks, lc.lds, lc.feat, k_begin, k_end};
     e = ra ? enqueue_round_pass(q, w, k, req, *ra, kp, sl.params, a)
         : w.n_rounds ? enqueue_rounds(q, w, k, req, kp, sl.params, a)
-                     : enqueue_frame(q, w, req, sl.params, a, pass != nullptr);
+                     : enqueue_frame(q, w, req, sl.params, a, pass != nullptr, vw != nullptr);
     if (e != GS_OK) return e;
     HIPCHK(hipEventRecord(sl.done, st));
     sl.used = true;

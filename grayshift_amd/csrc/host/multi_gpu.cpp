@@ -180,7 +180,7 @@ struct gs_multi {
     bool plan = false;
     mutable std::mutex mu;  // one frame at a time; guards every field below and comms_broken
     // tile partition of the last camera (plan or round-robin)
-    bool part_ready = false;
+    bool part_ready = false, part_rr = false;  // (part_rr: cut round-robin for a views call)
     gs_camera part_cam{};
     std::vector<int32_t> order;  // empty: round-robin
     int32_t slots = 0;
@@ -258,11 +258,19 @@ struct gs_multi {
         return fail(GS_ERR_HIP, what);
     }
 
-    gs_status partition(const gs_camera* cam, uint64_t seed, double* plan_ms);
+    // round_robin: no cost plan whatever `plan` says (a views call's tall frame)
+    gs_status partition(const gs_camera* cam, uint64_t seed, double* plan_ms, bool round_robin = false);
     // pass_samples != 0: a pass of the open accumulation (cam, ss and seed are then its own)
     // adapt: a pass of the open adaptation, of adapt_rounds rounds (0: resolve the state as it stands)
+    // vw: a views call (cam is then the tall frame's camera, ss one batch of its samples; the
+    // views' own seeds)
+    struct ViewsCall {
+        const gs_view* views;
+        uint32_t n, chunk;
+    };
     gs_status render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, const gs_multi_outputs* out,
-                     gs_stats* stats, uint32_t pass_samples = 0, bool adapt = false, uint32_t adapt_rounds = 0);
+                     gs_stats* stats, uint32_t pass_samples = 0, bool adapt = false, uint32_t adapt_rounds = 0,
+                     const ViewsCall* vw = nullptr);
     gs_status accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk);
     void accum_end();
     // The tile (or -1) of rank `rank`'s slot `slot`, and the slots the rank holds.
@@ -286,14 +294,14 @@ struct gs_multi {
     void permute_rank(int rank, const gs_camera& cam, uint8_t* image, uint8_t* packed, size_t elem, bool to_image) const;
 };
 
-gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_ms) {
-    if (part_ready && std::memcmp(&part_cam, cam, sizeof(gs_camera)) == 0) return GS_OK;
+gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_ms, bool round_robin) {
+    if (part_ready && part_rr == round_robin && std::memcmp(&part_cam, cam, sizeof(gs_camera)) == 0) return GS_OK;
     const auto t0 = std::chrono::steady_clock::now();
     const int n = (int)dev.size();
     part_ready = false;
     order.clear();
     slots = 0;
-    if (plan && n > 1) {
+    if (plan && n > 1 && !round_robin) {
         HIPOK(hipSetDevice(dev[0].id));
         gs_status s = gs_plan_tiles(dev[0].scene, cam, seed, n, tw, th, nullptr, 0, &slots);
         if (s != GS_OK) return s;
@@ -312,6 +320,7 @@ gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_
         if (cap < 0) return fail(GS_ERR_ARG, "bad partition");
     }
     part_cam = *cam;
+    part_rr = round_robin;
     part_ready = true;
     *plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return GS_OK;
@@ -319,7 +328,7 @@ gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_
 
 gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                            const gs_multi_outputs* out, gs_stats* stats, uint32_t pass_samples, bool adapt,
-                           uint32_t adapt_rounds) {
+                           uint32_t adapt_rounds, const ViewsCall* vw) {
     if (!cam || !ss) return fail(GS_ERR_ARG, "null argument");
     if (out && !out->rgb && !out->rgb8 && !out->ppm_text) return fail(GS_ERR_ARG, "no output requested");
     if (out && out->ppm_text && !out->ppm_len) return fail(GS_ERR_ARG, "ppm_text without ppm_len");
@@ -335,7 +344,7 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
     const auto t0 = std::chrono::steady_clock::now();
     const int n = (int)dev.size();
     double plan_ms = 0.0;
-    gs_status s = partition(cam, seed, &plan_ms);
+    gs_status s = partition(cam, seed, &plan_ms, vw != nullptr);
     if (s != GS_OK) return s;
     {
         // The scenes' placement pilots (first frame, launch.cpp, run before the first launch):
@@ -345,7 +354,8 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         for (int i = 0; i < n; i++) sc[i] = dev[i].scene, st[i] = dev[i].stream;
         const auto tp = std::chrono::steady_clock::now();
         int ran = 0;
-        s = gs_placement_prepare(sc.data(), ids.data(), st.data(), n, cam, ss, &ran);
+        // (a views call: view 0's own camera and frame)
+        s = gs_placement_prepare(sc.data(), ids.data(), st.data(), n, vw ? &vw->views[0].cam : cam, ss, &ran);
         if (s != GS_OK) return s;
         if (ran) plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
     }
@@ -383,6 +393,9 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
             s = gs_render_tiles_pass_timed_async(d.scene, cam, pass_samples, seed, &p, (uint32_t)acc_samples, acc_chunk,
                                                  (double*)d.sums.p, (double*)d.delta.p, &o, (gs_counters*)d.cnt.p,
                                                  d.stream, d.ev[2], d.ev[3], direct, true);
+        } else if (vw) {
+            s = gs_render_tiles_views_timed_async(d.scene, vw->views, vw->n, ss->batch_size, vw->chunk, &p, &o,
+                                                  (gs_counters*)d.cnt.p, d.stream, d.ev[2], d.ev[3], direct, true);
         } else {
             s = gs_render_tiles_timed_async(d.scene, cam, ss, seed, &p, &o, (gs_counters*)d.cnt.p, d.stream, d.ev[2],
                                             d.ev[3], direct, true);
@@ -1022,6 +1035,24 @@ gs_status gs_multi_render(gs_multi* m, const gs_camera* cam, const gs_sample_set
     if (!m) return fail(GS_ERR_ARG, "null context");
     std::lock_guard<std::mutex> lock(m->mu);
     return m->render(cam, ss, seed, out, stats);
+}
+
+gs_status gs_multi_render_views(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t samples, uint32_t chunk,
+                                const gs_multi_outputs* out, gs_stats* stats) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (out && out->ppm_text) return fail(GS_ERR_ARG, "a views call writes no PPM text");
+    const uint32_t c = chunk ? chunk : 16u;
+    gs_camera tall;
+    gs_status s = gs_views_check(m->dev[0].scene, views, n_views, samples, c, &tall);
+    if (s != GS_OK) return s;
+    // (rank 0 holds the most tiles of the round-robin cut: its share bounds every rank's)
+    const gs_partition p0{0, (int32_t)m->dev.size(), m->tw, m->th, nullptr, 0, 0};
+    s = gs_views_check_cap(gs_partition_capacity(&tall, &p0), samples, c);
+    if (s != GS_OK) return s;
+    const gs_sample_settings ss{0.0, 0.0, samples, 0};
+    const gs_multi::ViewsCall vw{views, n_views, c};
+    return m->render(&tall, &ss, 0, out, stats, 0, false, 0, &vw);
 }
 
 gs_status gs_multi_frame(const gs_multi* m, const float** d_rgb, const uint8_t** d_rgb8, int32_t* device) {

@@ -65,6 +65,9 @@ struct LaunchSlot {
     // GS_FEAT_NESTED: each lane's save slots (KParams::nest_save), 8 slot-major arrays of 8 B per lane of the grid
     double* nest_save = nullptr;
     size_t nest_save_bytes = 0;
+    // a views launch's records (KParams::views)
+    gs_view* views = nullptr;
+    size_t views_bytes = 0;
 };
 static const int kLaunchSlots = 4;
 

@@ -1030,6 +1030,7 @@ gs_status gs_device_scene_destroy(gs_device_scene* ds) {
         if (sl.partial) (void)hipFree(sl.partial);
         if (sl.rbuf) (void)hipFree(sl.rbuf);
         if (sl.nest_save) (void)hipFree(sl.nest_save);
+        if (sl.views) (void)hipFree(sl.views);
     }
     if (ds->mem) (void)hipFree(ds->mem);
     delete ds;

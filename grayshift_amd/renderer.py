@@ -1,6 +1,8 @@
 """Python entry points to the device path (libgrayshift.so, HIP for gfx950).
 
 * ``render(scene)`` — the one-call ``Camera::render`` replacement (linear f32 frame).
+* ``render_views(scene, cameras, samples)`` / ``MultiRenderer.render_views`` — a batch of
+  cameras of one world in a single launch, each view bit-identical to its own render.
 * ``ProgressiveRenderer`` — a fixed-spp frame as a sequence of passes over device-resident
   f64 sums: preview, add samples, checkpoint, resume (bit-identical to the one-shot render).
 * ``AdaptiveRenderer`` — the scene's own adaptive SampleSettings in passes of batch rounds:
@@ -158,6 +160,47 @@ class MultiRenderer:
         N.check(N.lib.gs_multi_render(self.handle, C.byref(self.cam), C.byref(self.settings), seed, None,
                                       C.byref(st)))
 
+    def views_chunk(self, cam, samples):
+        """gs_views_chunk: the coarse chunk a one-shot render of `cam` (a gs_camera) at `samples`
+        spp takes under the process's knobs as they stand."""
+        d = C.c_void_p()
+        N.check(N.lib.gs_multi_scene(self.handle, 0, C.byref(d)))
+        c = N.lib.gs_views_chunk(d, C.byref(cam), samples)
+        if c == 0:
+            raise N.GrayshiftError(N.GS_ERR_ARG, N.lib.gs_last_error().decode("utf-8", "replace"))
+        return c
+
+    def render_views(self, cameras, samples, seeds=None, chunk=0, rgb=True, rgb8=False):
+        """V cameras (gs_camera_specs of one width and height) of the context's world in one
+        launch (gs_multi_render_views), `samples` per pixel, view v with seed seeds[v] (default 1).
+        View v's frames are bit for bit those of a fixed-spp render of cameras[v] with that seed
+        and the same coarse chunk; chunk=0 takes gs_views_chunk, the chunk of plain render()
+        calls.  Returns a dict like render(): "rgb" [V,H,W,3] f32, "rgb8" [V,H,W,3] u8, the
+        summed "counters", "stats".  With no host output the frames stay on the first device
+        (frame_ptr(): [V,H,W,3] f32)."""
+        cams = [camera(c) for c in cameras]
+        V = len(cams)
+        seeds = [1] * V if seeds is None else list(seeds)
+        if len(seeds) != V:
+            raise ValueError("one seed per camera")
+        views = (N.gs_view * max(V, 1))()
+        for v in range(V):
+            views[v].cam = cams[v]
+            views[v].seed = seeds[v]
+        if V and not chunk:
+            chunk = self.views_chunk(cams[0], samples)
+        W, H = (cams[0].image_width, cams[0].image_height) if V else (0, 0)
+        out, res, _ = _outputs(W, V * H, rgb, rgb8, False)
+        st = N.gs_stats()
+        N.check(N.lib.gs_multi_render_views(self.handle, views, V, samples, chunk,
+                                            C.byref(out) if out is not None else None, C.byref(st)))
+        for k in ("rgb", "rgb8"):
+            if k in res:
+                res[k] = res[k].reshape(V, H, W, 3)
+        res["counters"] = st.counters.as_dict()
+        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+        return res
+
     def scene_info(self, rank=0):
         """gs_device_scene_info of the scene on rank `rank`'s device."""
         d = C.c_void_p()
@@ -184,6 +227,37 @@ class MultiRenderer:
             self.close()
         except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
             pass
+
+
+def render_views(scene, cameras, samples, seeds=None, num_gpus=1, tile=64, devices=None, **kw):
+    """MultiRenderer.render_views in one call: upload `scene`, render the cameras, free it.  A
+    batch whose chunk sums exceed the partial budget is rendered as consecutive groups of cameras
+    that fit, the results concatenated: grouping changes no bit (the views contract).  Returns
+    MultiRenderer.render_views' dict; "stats" is then a list, one gs_stats dict per group.
+    **kw: render_views' chunk, rgb, rgb8."""
+    r = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices)
+    try:
+        cameras = list(cameras)
+        seeds = [1] * len(cameras) if seeds is None else list(seeds)
+        if len(seeds) != len(cameras):
+            raise ValueError("one seed per camera")
+        group = max(1, len(cameras))
+        parts, at = [], 0
+        while at < len(cameras) or not parts:
+            try:
+                parts.append(r.render_views(cameras[at:at + group], samples, seeds[at:at + group], **kw))
+            except N.GrayshiftError as e:
+                if e.code != N.GS_ERR_ARG or "partial budget" not in str(e) or group == 1:
+                    raise
+                group = (group + 1) // 2
+                continue
+            at += group
+        res = {k: np.concatenate([p[k] for p in parts]) for k in ("rgb", "rgb8") if k in parts[0]}
+        res["counters"] = {k: sum(p["counters"][k] for p in parts) for k in parts[0]["counters"]}
+        res["stats"] = [p["stats"] for p in parts] if len(parts) > 1 else parts[0]["stats"]
+        return res
+    finally:
+        r.close()
 
 
 class ProgressiveRenderer:

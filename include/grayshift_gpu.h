@@ -648,6 +648,67 @@ gs_status gs_multi_adapt_upload(gs_multi* m, const gs_camera* cam, const gs_samp
                                 const gs_counters* counters);
 gs_status gs_multi_adapt_end(gs_multi* m);
 
+/* ---- Views: a batch of cameras in one launch (additive: the ABI stays 11, no existing call changes) ----
+ * V cameras of one device-resident scene at a fixed number of samples per pixel, all of the same
+ * width W and height H: turntables, camera paths, stereo pairs, the faces of an environment probe.
+ * The batch runs as one tall frame of W x (V H) pixels, view v in rows [v H, (v + 1) H): one
+ * parameter upload, one megakernel launch, one queue drain and one resolve for all of them.
+ *
+ * The contract: view v's linear f32 frame and rgb8 frame are, bit for bit, what a one-shot
+ * fixed-spp render of views[v].cam gives with seed views[v].seed and the same coarse chunk
+ * (gs_render / gs_multi_render; gs_render_tiles_pass_async at sample_base 0), and the call's
+ * counters are the exact sums of those V renders' counters.  The number of views in the call,
+ * their order, the other cameras in the batch, the rank count, the tile size and the guided tail
+ * move no bit: sample s of pixel p of a view draws from stream_seed(seed, p, s) with p the pixel's
+ * index in its own W x H frame, and a pixel's sum is ((0 + C_0) + C_1) + ... over chunk sums of
+ * `chunk` samples -- everything else is scheduling.  Views may differ in every camera field but
+ * the size: lanes of one wave may hold different views, with and without defocus, of different
+ * max_depth.
+ *
+ * Fixed spp only (no adaptive settings, progressive passes or PPM text over views).  A scene that
+ * needs the catch-all kernel (compositions beyond the reference scenes': gs_scene_info.feat & 512)
+ * returns GS_ERR_UNSUPPORTED: that kernel has no views form.
+ *
+ * Argument checks, all before any device work, each GS_ERR_ARG with a gs_last_error message: a
+ * NULL pointer (d_counters / stats may be), n_views == 0, views that differ in width or height,
+ * any max_depth == 0, samples == 0 or not a multiple of c, samples / c > 64, V W H or the item
+ * count not fitting 32 bits, chunk sums (capacity * samples / c * 24 bytes) over the partial
+ * budget (4 GiB).  Where the scene's placement pilot has not run yet it runs with view 0's camera;
+ * it never changes a result. */
+typedef struct gs_view {
+    gs_camera cam;
+    uint64_t seed;
+} gs_view;
+
+/* The tile-level primitive, stateless, the sibling of gs_render_tiles_pass_async: renders this
+ * rank's tiles of the tall frame into packed device buffers (out->rgb / out->rgb8, at least one;
+ * padding pixels get 0; out->item_visits must be NULL).  `part` cuts the tall frame:
+ * gs_partition_capacity on a camera with image_height = V H gives the capacity, and
+ * gs_unpack_tiles_part_async with that camera scatters the ranks' buffers into [V][H][W][3].
+ * views: host array, read before the call returns.  chunk: the coarse chunk c, 0 = 16, taken as
+ * given (gs_views_chunk gives a one-shot render's); the launch is always chunked.  d_counters is
+ * accumulated into. */
+gs_status gs_render_tiles_views_async(const gs_device_scene* scene, const gs_view* views, uint32_t n_views,
+                                      uint32_t samples, uint32_t chunk, const gs_partition* part,
+                                      const gs_render_outputs* out, gs_counters* d_counters, void* stream);
+
+/* One synchronous batch on the frame context, like gs_multi_render: out->rgb / out->rgb8 are
+ * [V][H][W][3] (ppm_text must be NULL), NULL `out` leaves the frames on the first device
+ * (gs_multi_frame: a W x (V H) frame).  Tiles are assigned round-robin whatever the context's
+ * `plan` setting: the cost pilot behind a plan is a one-camera notion.  GS_ERR_ARG while an
+ * accumulation or adaptation is open, as gs_multi_render. */
+gs_status gs_multi_render_views(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t samples,
+                                uint32_t chunk, const gs_multi_outputs* out, gs_stats* stats);
+
+/* The coarse chunk a one-shot fixed-spp render (gs_render / gs_multi_render at `samples` spp,
+ * under the process's knobs as they stand) of one view's W x H frame takes -- of that frame, not
+ * of the tall one: the small-frame rule makes c depend on the frame size.  A views call with
+ * this chunk equals plain renders of each camera (a render that does not split its pixels sums
+ * them as one chunk of `samples`).  scene NULL: the rule for a scene whose samples are alike (no
+ * media, no BVHs under instances, no staged shading: feat & 19 == 0).  0: bad arguments.  A chunk that does not divide `samples` is
+ * the one-shot render's all the same, but a views call refuses it. */
+uint32_t gs_views_chunk(const gs_device_scene* scene, const gs_camera* cam, uint32_t samples);
+
 /* Path of the RCCL library gs_render_multi uses (loaded on this call), or NULL. */
 const char* gs_rccl_library(void);
 
