@@ -187,6 +187,7 @@ extern "C" {
     pub fn gs_debug_record_visits(scene: *const gs_device_scene, cam: *const gs_camera, ss: *const gs_sample_settings,
                                   seed: u64, part: *const gs_partition, d_packed_rgb: *mut f32, d_visits: *mut u32,
                                   stream: *mut c_void) -> gs_status;
+    pub fn gs_debug_last_launch_feat(scene: *const gs_device_scene, feat: *mut i32) -> gs_status;
     pub fn gs_device_scene_create(scene: *const gs_flat_scene, out: *mut *mut gs_device_scene) -> gs_status;
     pub fn gs_device_scene_destroy(scene: *mut gs_device_scene) -> gs_status;
     pub fn gs_device_scene_info(scene: *const gs_device_scene, out: *mut gs_scene_info) -> gs_status;

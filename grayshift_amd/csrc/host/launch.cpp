@@ -821,6 +821,12 @@ struct Enqueue {
     size_t lds;
     int feat;  // the launch shape's instantiation (LaunchCfg::feat)
     hipEvent_t k_begin, k_end;
+    const gs_device_scene* ds;
+    // kernel_for(f), noted for gs_debug_last_launch_feat
+    void (*kernel(int f) const)(KArgs) {
+        ds->last_launch_feat.store(f);
+        return kernel_for(f);
+    }
 };
 
 // Batch rounds: init (every real packed pixel active), then per round and segment: parameters,
@@ -839,7 +845,7 @@ static gs_status enqueue_rounds(const Enqueue& q, const WorkPlan& w, const Knobs
     // paths always trace a camera ray take the fixed kernel's sample loop (GS_FEAT_RSPLIT).
     const bool rsplit = GS_USE_RSPLIT && has_rsplit(q.feat) && r.cam->max_depth > 0 &&
                         (k.sample_chunk > 0 || r.ss->batch_size > GS_ROUND_WHOLE_MAX_BATCH || k.round_whole == 0);
-    void (*rkern)(KArgs) = kernel_for(rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat);
+    void (*rkern)(KArgs) = q.kernel(rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat);
     for (uint32_t rd = 0; rd < w.n_rounds; rd++)
         for (uint32_t sg = 0; sg < w.n_segs; sg++) {
             HIPCHK(launch_round_params_kernel(st, dP, rd, sg, w.seg_px, k.sample_chunk, k.round_whole));
@@ -865,7 +871,7 @@ static gs_status enqueue_round_pass(const Enqueue& q, const WorkPlan& w, const K
     if (q.k_begin) HIPCHK(hipEventRecord(q.k_begin, st));
     const unsigned g_fold = (unsigned)std::min<int64_t>((w.seg_px + 255) / 256, 8192);
     const bool rsplit = GS_USE_RSPLIT && has_rsplit(q.feat) && r.cam->max_depth > 0;
-    void (*rkern)(KArgs) = kernel_for(rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat);
+    void (*rkern)(KArgs) = q.kernel(rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat);
     for (uint32_t rd = ra.first_round; rd < ra.first_round + ra.rounds; rd++)
         for (uint32_t sg = 0; sg < w.n_segs; sg++) {
             HIPCHK(launch_round_params_kernel(st, dP, rd, sg, w.seg_px, k.sample_chunk, 0));
@@ -889,7 +895,7 @@ static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const Launch
     const int feat = views         ? q.feat | GS_FEAT_FIXED | GS_FEAT_VIEWS
                      : pilot_kernel ? GS_FEAT_PILOT
                                     : q.feat | (fixed ? GS_FEAT_FIXED : 0);
-    HIPCHK(launch_render_kernel(q.st, kernel_for(feat), q.blocks, q.lds, a));
+    HIPCHK(launch_render_kernel(q.st, q.kernel(feat), q.blocks, q.lds, a));
     if (q.k_end) HIPCHK(hipEventRecord(q.k_end, q.st));
     if (pass) {  // (always chunked: the pass's sums join the frame's)
         HIPCHK(launch_accumulate_kernel(q.st, dP, r.cap));
@@ -1012,7 +1018,7 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     a.P = sl.params;
     if (outs->item_visits) HIPCHK(hipMemsetAsync(outs->item_visits, 0, (size_t)cap * sizeof(uint32_t), st));
     HIPCHK(launch_params_kernel(st, kp, sl.params));  // (zeroes the queue)
-    const Enqueue q{st, (unsigned)blocks, lc.lds, lc.feat, k_begin, k_end};
+    const Enqueue q{st, (unsigned)blocks, lc.lds, lc.feat, k_begin, k_end, ds};
     e = ra ? enqueue_round_pass(q, w, k, req, *ra, kp, sl.params, a)
         : w.n_rounds ? enqueue_rounds(q, w, k, req, kp, sl.params, a)
                      : enqueue_frame(q, w, req, sl.params, a, pass != nullptr, vw != nullptr);
@@ -1272,6 +1278,12 @@ gs_status gs_debug_record_visits(const gs_device_scene* ds, const gs_camera* cam
     gs_render_outputs o{d_packed_rgb, nullptr, nullptr};
     VisitArgs va{d_visits, ds->node_records};
     return launch(ds, cam, ss, seed, part, &o, nullptr, stream, nullptr, nullptr, &va);
+}
+
+gs_status gs_debug_last_launch_feat(const gs_device_scene* ds, int32_t* feat) {
+    if (!ds || !feat) return fail(GS_ERR_ARG, "null argument");
+    *feat = ds->last_launch_feat.load();
+    return GS_OK;
 }
 
 gs_status gs_device_alloc(int64_t bytes, void** d_out) {

@@ -104,6 +104,9 @@ struct gs_device_scene {
     uint32_t bvh_depth = 1;  // top-level BVH depth (informational: the walk keeps no stack)
     bool cert_boxes = false;  // every top-level node coordinate |x| <= 1e15 (box_cert applies)
     int feat = 0;             // GS_FEAT_* of the kernel instantiation to launch
+    // Test hook (gs_debug_last_launch_feat): the feature word the most recent render-kernel
+    // launch of this scene passed to kernel_for (-1: no launch yet).  Host only.
+    mutable std::atomic<int32_t> last_launch_feat{-1};
     const TQuad* tquads = nullptr;  // every quad's traversal record, gs_quad order
     uint32_t thr_root = THR_END;    // the threaded tree's first link (THR_*)
     MirrorPrefix mirror;            // mirrored prefixes (per block) of the current placement

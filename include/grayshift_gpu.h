@@ -302,6 +302,13 @@ gs_status gs_debug_set_partial_budget(uint64_t bytes);
  * same bits.  fine_chunk > 1 is rejected (GS_ERR_ARG). */
 gs_status gs_debug_set_guided_tail(int32_t fine_chunk, int32_t tail_pct);
 
+/* Test hook: the kernel feature word (gs_scene_info.feat's bits, plus 128 fixed-spp, 1024 split
+ * batch round, 2048 views) that the scene's most recent render-kernel launch selected its
+ * instantiation with -- the scene's own choice after the launch's changes (8 cleared when the
+ * LDS mirror is a strict prefix; the fixed, round and views forms added).  -1 before any launch.
+ * Host only: read after the call that enqueued the launch returned. */
+gs_status gs_debug_last_launch_feat(const gs_device_scene* scene, int32_t* feat);
+
 /* Upload a flattened scene to the current HIP device. */
 gs_status gs_device_scene_create(const gs_flat_scene* scene, gs_device_scene** out);
 gs_status gs_device_scene_destroy(gs_device_scene* scene);

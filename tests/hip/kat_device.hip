@@ -170,6 +170,128 @@ __global__ void k_noise(int n, int which, const uint8_t* perm, double scale, con
     out[i] = which == 0 ? perlin3(perm, q[0], q[1], q[2]) : noise_value(perm, scale, q[0], q[1], q[2]);
 }
 
+// quad_accept over the product's own quad records (the host's normal, D and w derivation).
+__global__ void k_quad(int n, const gs_quad* q, const double* ray, const double* iv, double* t, int* hit) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r;
+    r.o = mk(ray[6 * i], ray[6 * i + 1], ray[6 * i + 2]);
+    r.d = mk(ray[6 * i + 3], ray[6 * i + 4], ray[6 * i + 5]);
+    r.time = 0.0;
+    double tt = 0.0;
+    hit[i] = quad_accept(q[i], r, iv[2 * i], iv[2 * i + 1], tt) ? 1 : 0;
+    t[i] = tt;
+}
+
+// The sphere tests of the leaf runs.  which: 0 sphere_accept_rr_ra; 1 sphere_disc_rr, then
+// sphere_root_take for a real discriminant; 2 the same with sphere_root_take_ra.  As in the
+// megakernel, rr = r * r is taken once and ra = rcp_cert(a); the _ra forms are for a in
+// [2^-900, 2^900] (the caller's cases).
+__global__ void k_sphere_run(int n, int which, const double* sph, const double* ray, const double* iv, double* t,
+                             int* hit) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r;
+    r.o = mk(ray[6 * i], ray[6 * i + 1], ray[6 * i + 2]);
+    r.d = mk(ray[6 * i + 3], ray[6 * i + 4], ray[6 * i + 5]);
+    r.time = 0.0;
+    const d3 c = mk(sph[4 * i], sph[4 * i + 1], sph[4 * i + 2]);
+    const double rr = sph[4 * i + 3] * sph[4 * i + 3];
+    const double a = len2(r.d), ra = rcp_cert(a);
+    const double tmin = iv[2 * i], tmax = iv[2 * i + 1];
+    double tt = 0.0;
+    bool h;
+    if (which == 0) {
+        h = sphere_accept_rr_ra(c, rr, r, a, ra, tmin, tmax, tt);
+    } else {
+        const SphereDisc q = sphere_disc_rr(c, rr, r, a);
+        const bool real = !(q.disc < 0.0);
+        h = real && (which == 1 ? sphere_root_take(q.h, q.disc, a, tmin, tmax, tt)
+                                : sphere_root_take_ra(q.h, q.disc, a, ra, tmin, tmax, tt));
+    }
+    hit[i] = h ? 1 : 0;
+    t[i] = tt;
+}
+
+// which: 0 box_hit, 1 box_hit_v, 2 box_hit_fast (-1 where fast_slab_ray does not hold: the
+// megakernel does not call it there)
+__global__ void k_box(int n, int which, const double* box, const double* ray, const double* iv, int* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    DNode nd{box[6 * i], box[6 * i + 1], box[6 * i + 2], box[6 * i + 3], box[6 * i + 4], box[6 * i + 5], 0, 0, 0, 0};
+    d3 o = mk(ray[6 * i], ray[6 * i + 1], ray[6 * i + 2]);
+    d3 d = mk(ray[6 * i + 3], ray[6 * i + 4], ray[6 * i + 5]);
+    d3 inv = mk(1.0 / d.x, 1.0 / d.y, 1.0 / d.z);
+    const double tmin = iv[2 * i], tmax = iv[2 * i + 1];
+    int r;
+    if (which == 0) r = box_hit(nd, o, inv, tmin, tmax) ? 1 : 0;
+    else if (which == 1) r = box_hit_v(nd, o, inv, tmin, tmax) ? 1 : 0;
+    else r = fast_slab_ray(o, inv) ? (box_hit_fast(nd, o, inv, tmin, tmax) ? 1 : 0) : -1;
+    out[i] = r;
+}
+
+// A chain of up to three instances per case (kind 0: none): inst_forward on the ray outermost
+// first, then inst_backward on (p, n) innermost first, as the megakernel walks a chain.
+__global__ void k_inst(int n, const int* kind, const double* par, const double* ray, const double* pn, double* ray_out,
+                       double* pn_out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    gs_instance in[3];
+    for (int k = 0; k < 3; k++) {
+        in[k].kind = (uint32_t)kind[3 * i + k];
+        in[k].child = 0;
+        for (int j = 0; j < 3; j++) in[k].p[j] = par[9 * i + 3 * k + j];
+    }
+    Ray r;
+    r.o = mk(ray[6 * i], ray[6 * i + 1], ray[6 * i + 2]);
+    r.d = mk(ray[6 * i + 3], ray[6 * i + 4], ray[6 * i + 5]);
+    r.time = 0.0;
+    for (int k = 0; k < 3; k++)
+        if (in[k].kind) inst_forward(in[k], r);
+    d3 p = mk(pn[6 * i], pn[6 * i + 1], pn[6 * i + 2]), nn = mk(pn[6 * i + 3], pn[6 * i + 4], pn[6 * i + 5]);
+    for (int k = 2; k >= 0; k--)
+        if (in[k].kind) inst_backward(in[k], p, nn);
+    const double ro[6] = {r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z};
+    const double po[6] = {p.x, p.y, p.z, nn.x, nn.y, nn.z};
+    for (int j = 0; j < 6; j++) {
+        ray_out[6 * i + j] = ro[j];
+        pn_out[6 * i + j] = po[j];
+    }
+}
+
+// which: 0 reflect(v, n), 1 refract(v, n, ratio)
+__global__ void k_vec(int n, int which, const double* v, const double* nrm, const double* ratio, double* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const d3 a = mk(v[3 * i], v[3 * i + 1], v[3 * i + 2]), b = mk(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]);
+    const d3 r = which == 0 ? reflect(a, b) : refract(a, b, ratio[i]);
+    out[3 * i] = r.x;
+    out[3 * i + 1] = r.y;
+    out[3 * i + 2] = r.z;
+}
+
+__global__ void k_color_byte(int n, const double* c, int* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = (int)color_byte(c[i]);
+}
+
+// which: 0 sat_i32 (sign-extended), 1 sat_u64 clamped to u64 (HDRI::sample's `as usize`),
+// 2 sat_u64 clamped to u32
+__global__ void k_sat(int n, int which, const double* f, uint64_t* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = which == 0   ? (uint64_t)(int64_t)sat_i32(f[i])
+             : which == 1 ? sat_u64(f[i], 18446744073709551616.0, ~0ull)
+                          : sat_u64(f[i], 4294967295.0, 4294967295ull);
+}
+
+__global__ void k_udiv(int n, const uint32_t* num, const UDiv* u, uint32_t* out) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = udiv(num[i], u[i]);
+}
+
 extern "C" {
 
 int kat_aabb(int n, const double* box, const double* ray, const double* iv, int* out) {
@@ -269,6 +391,91 @@ int kat_noise(int n, int which, const uint8_t* perm256, double scale, const doub
     hipLaunchKernelGGL(k_noise, grid(n), dim3(256), 0, 0, n, which, dperm, scale, dp, dout);
     back(out, dout, n);
     (void)hipFree(dperm); (void)hipFree(dp);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+int kat_quad(int n, const void* quads, const double* ray, const double* iv, double* t, int* hit) {
+    gs_quad* dq = dcopy((const gs_quad*)quads, (size_t)n);
+    double *dr = dcopy(ray, 6 * (size_t)n), *di = dcopy(iv, 2 * (size_t)n);
+    double* dt = dcopy<double>(nullptr, n);
+    int* dh = dcopy<int>(nullptr, n);
+    hipLaunchKernelGGL(k_quad, grid(n), dim3(256), 0, 0, n, dq, dr, di, dt, dh);
+    back(t, dt, n);
+    back(hit, dh, n);
+    (void)hipFree(dq); (void)hipFree(dr); (void)hipFree(di);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+int kat_sphere_run(int n, int which, const double* sph, const double* ray, const double* iv, double* t, int* hit) {
+    double *ds = dcopy(sph, 4 * (size_t)n), *dr = dcopy(ray, 6 * (size_t)n), *di = dcopy(iv, 2 * (size_t)n);
+    double* dt = dcopy<double>(nullptr, n);
+    int* dh = dcopy<int>(nullptr, n);
+    hipLaunchKernelGGL(k_sphere_run, grid(n), dim3(256), 0, 0, n, which, ds, dr, di, dt, dh);
+    back(t, dt, n);
+    back(hit, dh, n);
+    (void)hipFree(ds); (void)hipFree(dr); (void)hipFree(di);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+int kat_box(int n, int which, const double* box, const double* ray, const double* iv, int* out) {
+    double *db = dcopy(box, 6 * (size_t)n), *dr = dcopy(ray, 6 * (size_t)n), *di = dcopy(iv, 2 * (size_t)n);
+    int* dout = dcopy<int>(nullptr, n);
+    hipLaunchKernelGGL(k_box, grid(n), dim3(256), 0, 0, n, which, db, dr, di, dout);
+    back(out, dout, n);
+    (void)hipFree(db); (void)hipFree(dr); (void)hipFree(di);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+int kat_inst(int n, const int* kind, const double* par, const double* ray, const double* pn, double* ray_out,
+             double* pn_out) {
+    int* dk = dcopy(kind, 3 * (size_t)n);
+    double *dp = dcopy(par, 9 * (size_t)n), *dr = dcopy(ray, 6 * (size_t)n), *dn = dcopy(pn, 6 * (size_t)n);
+    double *dro = dcopy<double>(nullptr, 6 * (size_t)n), *dpo = dcopy<double>(nullptr, 6 * (size_t)n);
+    hipLaunchKernelGGL(k_inst, grid(n), dim3(256), 0, 0, n, dk, dp, dr, dn, dro, dpo);
+    back(ray_out, dro, 6 * (size_t)n);
+    back(pn_out, dpo, 6 * (size_t)n);
+    (void)hipFree(dk); (void)hipFree(dp); (void)hipFree(dr); (void)hipFree(dn);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+int kat_vec(int n, int which, const double* v, const double* nrm, const double* ratio, double* out) {
+    double *dv = dcopy(v, 3 * (size_t)n), *dn = dcopy(nrm, 3 * (size_t)n), *dr = dcopy(ratio, n);
+    double* dout = dcopy<double>(nullptr, 3 * (size_t)n);
+    hipLaunchKernelGGL(k_vec, grid(n), dim3(256), 0, 0, n, which, dv, dn, dr, dout);
+    back(out, dout, 3 * (size_t)n);
+    (void)hipFree(dv); (void)hipFree(dn); (void)hipFree(dr);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+int kat_color_byte(int n, const double* c, int* out) {
+    double* dc = dcopy(c, n);
+    int* dout = dcopy<int>(nullptr, n);
+    hipLaunchKernelGGL(k_color_byte, grid(n), dim3(256), 0, 0, n, dc, dout);
+    back(out, dout, n);
+    (void)hipFree(dc);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+int kat_sat(int n, int which, const double* f, uint64_t* out) {
+    double* df = dcopy(f, n);
+    uint64_t* dout = dcopy<uint64_t>(nullptr, n);
+    hipLaunchKernelGGL(k_sat, grid(n), dim3(256), 0, 0, n, which, df, dout);
+    back(out, dout, n);
+    (void)hipFree(df);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+// udiv(num, udiv_make(den)): the magic made on the host, as the launches make it
+int kat_udiv(int n, const uint32_t* num, const uint32_t* den, uint32_t* out) {
+    UDiv* hu = new UDiv[(size_t)n > 0 ? (size_t)n : 1];
+    for (int i = 0; i < n; i++) hu[i] = gsd::udiv_make(den[i]);
+    uint32_t* dn = dcopy(num, n);
+    UDiv* du = dcopy(hu, n);
+    delete[] hu;
+    uint32_t* dout = dcopy<uint32_t>(nullptr, n);
+    hipLaunchKernelGGL(k_udiv, grid(n), dim3(256), 0, 0, n, dn, du, dout);
+    back(out, dout, n);
+    (void)hipFree(dn); (void)hipFree(du);
     return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
 }
 

@@ -20,6 +20,7 @@ from grayshift_amd import _native as N
 from grayshift_amd import scenes
 from grayshift_amd.scene import camera_spec, fixed_spp, sample_settings
 import oracle
+from tests import parity
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
@@ -64,6 +65,7 @@ def test_gpu_vs_oracle_small_configs(name):
     ref, rc = oracle.render(sc, seed=11)
     assert maxdiff(out, ref) < TOL
     assert counters_match(gc, rc)
+    parity.check(out, ref, same_association=True, label=name)  # 16 spp: one chunk per pixel
 
 
 @pytest.mark.parametrize("scene", ["hdri", "cornell_box", "earth", "checkered_spheres", "quads", "triangles"])
@@ -74,6 +76,7 @@ def test_gpu_vs_oracle_adaptive_sampling(scene):
     ref, rc = oracle.render(sc, seed=2)
     assert maxdiff(out, ref) < TOL
     assert counters_match(gc, rc)
+    parity.check(out, ref, same_association=True, label=scene)
 
 
 def test_bouncing_spheres_adaptive():
@@ -111,6 +114,7 @@ def test_odd_image_sizes(width, aspect):
     out, gc = g.render(sc, seed=9)
     ref, rc = oracle.render(sc, seed=9)
     assert out.shape == ref.shape and maxdiff(out, ref) < TOL and counters_match(gc, rc)
+    parity.check(out, ref, same_association=True, label="%dx%g" % (width, aspect))  # 4 spp: one chunk
 
 
 @pytest.mark.parametrize("depth", [0, 1, 2])
@@ -119,6 +123,7 @@ def test_shallow_max_depth(depth):
     out, gc = g.render(sc, seed=9)
     ref, rc = oracle.render(sc, seed=9)
     assert maxdiff(out, ref) < TOL and counters_match(gc, rc)
+    parity.check(out, ref, same_association=True, label="depth %d" % depth)
     if depth == 0:
         assert not out.any() and gc["rays"] == 0
 
@@ -130,6 +135,7 @@ def test_adaptive_edge_settings(batch, maxs, tol):
     out, gc = g.render(sc, seed=5)
     ref, rc = oracle.render(sc, seed=5)
     assert maxdiff(out, ref) < TOL and counters_match(gc, rc)
+    parity.check(out, ref, same_association=True, label="batch %d max %d" % (batch, maxs))
 
 
 def test_unsupported_scene_fails_cleanly():
@@ -247,6 +253,9 @@ def test_sample_chunks_match_oracle(name, chunk):
         out, gc = g.render(sc, seed=13)
     ref, rc = oracle.render(sc, seed=13)
     assert maxdiff(out, ref) < TOL and counters_match(gc, rc)
+    # 16 spp in chunks of 1, 3 or 5: several chunk sums per pixel, within 1 ulp of the oracle;
+    # one chunk of 16 and the unchunked loop (0) add in the oracle's order
+    parity.check(out, ref, same_association=chunk in (0, 16), label="%s chunk %d" % (name, chunk))
     with _chunk(0):
         whole, wc = g.render(sc, seed=13)
     assert wc == gc
