@@ -148,6 +148,13 @@ pub struct gs_view {
     pub cam: gs_camera, pub seed: u64,
 }
 
+/// An open views accumulation of the frame context (progressive views; additive, ABI 11).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_views_accum_info {
+    pub width: i32, pub height: i32, pub n_views: u32, pub chunk: u32, pub passes: u32, pub tile_h: i32,
+    pub counters: gs_counters,
+}
+
 /// An open adaptation of the frame context (progressive adaptive passes; additive, ABI 11).
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct gs_adapt_info {
@@ -288,6 +295,23 @@ extern "C" {
     pub fn gs_multi_render_views(m: *mut gs_multi, views: *const gs_view, n_views: u32, samples: u32, chunk: u32,
                                  out: *const gs_multi_outputs, stats: *mut gs_stats) -> gs_status;
     pub fn gs_views_chunk(scene: *const gs_device_scene, cam: *const gs_camera, samples: u32) -> u32;
+    // Progressive views (additive, ABI 11)
+    pub fn gs_views_tile_h(height: i32, tile_h: i32) -> i32;
+    pub fn gs_render_tiles_views_pass_async(scene: *const gs_device_scene, views: *const gs_view, n_views: u32,
+                                            view_samples: *const u32, selected: *const u8, samples: u32, chunk: u32,
+                                            part: *const gs_partition, d_sums: *mut f64,
+                                            out: *const gs_render_outputs, d_delta_partials: *mut f64,
+                                            d_counters: *mut gs_counters, stream: *mut c_void) -> gs_status;
+    pub fn gs_multi_views_accum_begin(m: *mut gs_multi, views: *const gs_view, n_views: u32, chunk: u32) -> gs_status;
+    pub fn gs_multi_views_accum_pass(m: *mut gs_multi, samples: u32, selected: *const u8,
+                                     out: *const gs_multi_outputs, stats: *mut gs_stats) -> gs_status;
+    pub fn gs_multi_views_accum_info(m: *const gs_multi, info: *mut gs_views_accum_info, view_samples_out: *mut u32,
+                                     delta_out: *mut f64) -> gs_status;
+    pub fn gs_multi_views_accum_download(m: *mut gs_multi, sums: *mut f64) -> gs_status;
+    pub fn gs_multi_views_accum_upload(m: *mut gs_multi, views: *const gs_view, n_views: u32, chunk: u32,
+                                       view_samples: *const u32, sums: *const f64,
+                                       counters: *const gs_counters) -> gs_status;
+    pub fn gs_multi_views_accum_end(m: *mut gs_multi) -> gs_status;
 }
 
 pub fn last_error() -> String {

@@ -186,6 +186,16 @@ class gs_view(C.Structure):
     _fields_ = [("cam", gs_camera), ("seed", C.c_uint64)]
 
 
+class gs_views_accum_info(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_views", C.c_uint32), ("chunk", C.c_uint32),
+                ("passes", C.c_uint32), ("tile_h", C.c_int32), ("counters", gs_counters)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "counters"}
+        d["counters"] = self.counters.as_dict()
+        return d
+
+
 # Every symbol include/*.h declares, with its ctypes signature.
 _P = C.c_void_p
 SIGNATURES = {
@@ -273,6 +283,18 @@ SIGNATURES = {
     "gs_multi_render_views": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.POINTER(gs_multi_outputs), C.POINTER(gs_stats)]),
     "gs_views_chunk": (C.c_uint32, [_P, C.POINTER(gs_camera), C.c_uint32]),
+    "gs_views_tile_h": (C.c_int32, [C.c_int32, C.c_int32]),
+    "gs_render_tiles_views_pass_async": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, _P, _P, C.c_uint32,
+                                                     C.c_uint32, C.POINTER(gs_partition), _P,
+                                                     C.POINTER(gs_render_outputs), _P, _P, _P]),
+    "gs_multi_views_accum_begin": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, C.c_uint32]),
+    "gs_multi_views_accum_pass": (C.c_int32, [_P, C.c_uint32, _P, C.POINTER(gs_multi_outputs),
+                                              C.POINTER(gs_stats)]),
+    "gs_multi_views_accum_info": (C.c_int32, [_P, C.POINTER(gs_views_accum_info), _P, _P]),
+    "gs_multi_views_accum_download": (C.c_int32, [_P, _P]),
+    "gs_multi_views_accum_upload": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, C.c_uint32, _P, _P,
+                                                C.POINTER(gs_counters)]),
+    "gs_multi_views_accum_end": (C.c_int32, [_P]),
     # grayshift_host.h
     "gs_host_scene_from_spec": (C.c_int32, [C.POINTER(gs_scene_spec), C.POINTER(_P)]),
     "gs_host_scene_destroy": (C.c_int32, [_P]),

@@ -25,7 +25,9 @@ An adaptive frame in progress (``AdaptiveRenderer``) is format ``ADAPTIVE_FORMAT
 * ``camera``, ``counters`` -- as above.
 
 ``read_checkpoint`` rejects it, and ``read_adaptive_checkpoint`` rejects format 1: neither
-renderer can resume the other's file.
+renderer can resume the other's file.  A batch of views in progress (``ViewsProgressiveRenderer``)
+is format ``VIEWS_FORMAT`` (3), described with its functions at the end of this file; its reader
+rejects formats 1 and 2, and their readers reject it.
 """
 import numpy as np
 
@@ -184,3 +186,107 @@ def check_adaptive_compatible(meta, width, height, settings, seed, camera):
             raise CheckpointError("checkpoint %s %r differs from the scene's %r" % (name, meta[name], get(name)))
     if bytes(meta["camera"]) != bytes(camera):
         raise CheckpointError("checkpoint camera differs from the scene's")
+
+
+# ------------------------------------------------------------------ progressive views (format 3)
+# A batch of views in progress (``ViewsProgressiveRenderer``):
+#
+# * ``sums``     -- [V, H, W, 3] f64, Σ of the samples' colours per pixel of every view, image order;
+# * ``samples``  -- [V] u32, the samples per pixel in each view's sums (whole chunks; they may differ);
+# * ``seeds``    -- [V] u64, the views' RNG seeds;
+# * ``cameras``  -- [V, sizeof(gs_camera)] u8, the bytes of each view's ``gs_camera``;
+# * ``chunk``, ``width``, ``height`` -- the coarse sample chunk and the size of one view;
+# * ``counters`` -- the cumulative work counters, in ``COUNTER_NAMES`` order;
+# * ``passes``, ``deltas`` ([V] f64) -- how many passes produced it and each view's last change.
+#
+# The three readers reject each other's files.
+VIEWS_FORMAT = 3
+VIEWS_REQUIRED = ("samples", "seeds", "cameras", "chunk", "width", "height", "counters")
+
+
+def _check_views(sums, meta):
+    v, h, w = len(meta["samples"]), meta["height"], meta["width"]
+    if v == 0:
+        raise CheckpointError("a views checkpoint of 0 views")
+    if sums.shape != (v, h, w, 3):
+        raise CheckpointError("sums of shape %r for %d views of %d x %d" % (sums.shape, v, w, h))
+    if len(meta["seeds"]) != v or len(meta["cameras"]) != v:
+        raise CheckpointError("%d sample counts, %d seeds, %d cameras" % (v, len(meta["seeds"]), len(meta["cameras"])))
+    if len({len(c) for c in meta["cameras"]}) != 1:
+        raise CheckpointError("cameras of different byte lengths")
+    if meta["chunk"] <= 0 or any(n < 0 or n % meta["chunk"] for n in meta["samples"]):
+        raise CheckpointError("samples %r are not whole chunks of %d" % (list(meta["samples"]), meta["chunk"]))
+
+
+def write_views_checkpoint(path, sums, meta):
+    """Write `sums` ([V, H, W, 3] f64) and `meta` to `path` (a file name, used as given, or a file
+    object).  meta: samples, seeds (V ints each), cameras (V byte strings), chunk, width, height
+    (ints), counters (a dict by COUNTER_NAMES); optional passes (int) and deltas (V floats)."""
+    for k in VIEWS_REQUIRED:
+        if k not in meta:
+            raise CheckpointError("checkpoint meta lacks %r" % k)
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    m = {"samples": [int(n) for n in meta["samples"]], "seeds": [int(s) for s in meta["seeds"]],
+         "cameras": [bytes(c) for c in meta["cameras"]], "chunk": int(meta["chunk"]), "width": int(meta["width"]),
+         "height": int(meta["height"])}
+    _check_views(sums, m)
+    v = len(m["samples"])
+    deltas = np.array(list(meta.get("deltas", [0.0] * v)), dtype=np.float64)
+    if deltas.shape != (v,):
+        raise CheckpointError("%d deltas for %d views" % (deltas.size, v))
+    counters = np.array([int(meta["counters"][n]) for n in COUNTER_NAMES], dtype=np.uint64)
+    fields = dict(format=np.int64(VIEWS_FORMAT), sums=sums, samples=np.array(m["samples"], dtype=np.uint32),
+                  seeds=np.array(m["seeds"], dtype=np.uint64),
+                  cameras=np.frombuffer(b"".join(m["cameras"]), dtype=np.uint8).reshape(v, -1),
+                  chunk=np.uint32(m["chunk"]), width=np.int32(m["width"]), height=np.int32(m["height"]),
+                  counters=counters, passes=np.uint32(int(meta.get("passes", 0))), deltas=deltas)
+    if hasattr(path, "write"):
+        np.savez(path, **fields)
+    else:
+        with open(path, "wb") as f:  # (the name as given: numpy would add ".npz" to it)
+            np.savez(f, **fields)
+
+
+def read_views_checkpoint(path):
+    """-> (sums [V, H, W, 3] f64, meta) as write_views_checkpoint took them."""
+    with np.load(path, allow_pickle=False) as z:
+        if "format" not in z.files or int(z["format"]) != VIEWS_FORMAT:
+            raise CheckpointError("not a grayshift views checkpoint (format %d)" % VIEWS_FORMAT)
+        for k in VIEWS_REQUIRED + ("sums",):
+            if k not in z.files:
+                raise CheckpointError("checkpoint lacks %r" % k)
+        sums = np.ascontiguousarray(z["sums"], dtype=np.float64)
+        cams = np.ascontiguousarray(z["cameras"], dtype=np.uint8)
+        if cams.ndim != 2:
+            raise CheckpointError("cameras of shape %r" % (cams.shape,))
+        meta = {"samples": [int(n) for n in z["samples"]], "seeds": [int(s) for s in z["seeds"]],
+                "cameras": [c.tobytes() for c in cams], "chunk": int(z["chunk"]), "width": int(z["width"]),
+                "height": int(z["height"]), "counters": {n: int(v) for n, v in zip(COUNTER_NAMES, z["counters"])},
+                "passes": int(z["passes"]) if "passes" in z.files else 0}
+        meta["deltas"] = [float(d) for d in z["deltas"]] if "deltas" in z.files else [0.0] * len(meta["samples"])
+    _check_views(sums, meta)
+    if len(meta["deltas"]) != len(meta["samples"]):
+        raise CheckpointError("%d deltas for %d views" % (len(meta["deltas"]), len(meta["samples"])))
+    return sums, meta
+
+
+def check_views_compatible(meta, width, height, chunk, seeds, cameras, samples=None):
+    """Raise CheckpointError unless the checkpoint's view count, size, chunk, seeds and camera bytes
+    are the ones given (the batch a caller resumes on) -- and, when `samples` is given, its per-view
+    sample vector too.  The world itself is not compared."""
+    seeds, cameras = [int(s) for s in seeds], [bytes(c) for c in cameras]
+    if len(meta["samples"]) != len(cameras) or len(seeds) != len(cameras):
+        raise CheckpointError("checkpoint of %d views, a batch of %d cameras and %d seeds" %
+                              (len(meta["samples"]), len(cameras), len(seeds)))
+    for name, have, want in (("width", meta["width"], int(width)), ("height", meta["height"], int(height)),
+                             ("chunk", meta["chunk"], int(chunk))):
+        if have != want:
+            raise CheckpointError("checkpoint %s %d differs from the batch's %d" % (name, have, want))
+    for v, (have, want) in enumerate(zip(meta["seeds"], seeds)):
+        if have != want:
+            raise CheckpointError("checkpoint seed %d of view %d differs from the batch's %d" % (have, v, want))
+    for v, (have, want) in enumerate(zip(meta["cameras"], cameras)):
+        if have != want:
+            raise CheckpointError("checkpoint camera of view %d differs from the batch's" % v)
+    if samples is not None and [int(n) for n in samples] != list(meta["samples"]):
+        raise CheckpointError("checkpoint samples %r differ from %r" % (list(meta["samples"]), [int(n) for n in samples]))

@@ -189,6 +189,12 @@ struct DevScene {
     const TLeaf* tleaves;
 };
 
+// One view of a progressive views pass (KParams::vstate): the samples its sums held before the
+// pass, and whether the pass renders it (1) or only resolves it again (0).
+struct GsViewState {
+    uint32_t before, selected;
+};
+
 // Cold launch parameters: written to device memory per launch and read through a
 // pointer at their (conditional) use sites, so they are not hoisted into SGPRs for
 // the whole kernel (a by-value struct of this size spilled SGPRs into VGPR lanes,
@@ -295,8 +301,28 @@ struct KParams {
     // the pixel's index inside its view.  Every other launch leaves these null / zero.
     const gs_view* views;  // [V] (device)
     UDiv u_vpx;            // W H, the pixels of one view
+    // Progressive views (gs_render_tiles_views_pass_async; DESIGN.md §3.2 "Progressive views"): a
+    // views launch that is also a pass, over a subset of the views.  `order` is then the launch's
+    // own tile order, in which the tiles of unselected views are empty slots (the megakernel
+    // retires their pixels without a ray), and gs_views_accumulate_kernel ends the pass: it finds
+    // a packed pixel's tile in vorder (the caller's order, every tile in its slot; null: tile =
+    // position) and its view's record in vstate.  Tiles do not straddle views (tile_h divides H),
+    // so each tile slot belongs to one view, and vdelta takes one partial sum of the pass's change
+    // per slot.  Every other launch leaves these null.
+    const GsViewState* vstate;  // [V] (device)
+    const int32_t* vorder;
+    double* vdelta;  // [capacity / (tile_w tile_h)] (nullable)
 };
 #define GS_ROUND_SUMMARY_WORDS 4
+
+// gs_view_state_kernel's argument: up to GS_VSTATE_BATCH of a views pass's per-view records by
+// value, written to dst[first, first + n) of the slot's array.
+#define GS_VSTATE_BATCH 256
+struct ViewStateBatch {
+    GsViewState s[GS_VSTATE_BATCH];
+    uint32_t first, n;
+};
+static_assert(sizeof(GsViewState) == 8 && sizeof(ViewStateBatch) <= 3072, "gs_view_state_kernel copies 8-byte words of a small argument");
 
 // gs_views_kernel's argument: up to GS_VIEW_BATCH of a views launch's records by value (a
 // kernel's arguments hold 4 KiB), written to views[first, first + n) of the slot's array.

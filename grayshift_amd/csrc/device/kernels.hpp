@@ -18,6 +18,12 @@ hipError_t launch_views_kernel(hipStream_t st, const ViewBatch& vb, gs_view* dst
 hipError_t launch_combine_kernel(hipStream_t st, unsigned grid, const KParams* P);
 // (a progressive pass's combine; its grid is gs_accum_blocks(capacity), the size of KParams::delta)
 hipError_t launch_accumulate_kernel(hipStream_t st, const KParams* P, uint32_t capacity);
+// (a progressive views pass: vb.n per-view records to dst + vb.first; the pass's tile order, n_pos
+// positions, written to dst after the parameter kernel -- it reads P; the pass's combine, one block
+// per tile slot of the rank, the size of KParams::vdelta)
+hipError_t launch_view_state_kernel(hipStream_t st, const ViewStateBatch& vb, GsViewState* dst);
+hipError_t launch_views_order_kernel(hipStream_t st, const KParams* P, int32_t* dst, uint32_t n_pos, uint32_t view_h);
+hipError_t launch_views_accumulate_kernel(hipStream_t st, const KParams* P, uint32_t slots);
 hipError_t launch_round_init_kernel(hipStream_t st, unsigned grid, const KParams* P);
 hipError_t launch_round_params_kernel(hipStream_t st, KParams* P, uint32_t round, uint32_t seg, uint32_t seg_px,
                                       int32_t chunk_req, int32_t whole_mode);

@@ -2469,6 +2469,133 @@ __global__ __launch_bounds__(256) void gs_accumulate_kernel(const KParams* __res
     if (threadIdx.x == 0 && P->delta) P->delta[blockIdx.x] = s_red[0];
 }
 
+// Progressive views: the per-view records of a pass, at most GS_VSTATE_BATCH per call, by value
+// like gs_views_kernel's.
+__global__ void gs_view_state_kernel(ViewStateBatch vb, GsViewState* __restrict__ dst) {
+    const uint64_t* src = reinterpret_cast<const uint64_t*>(vb.s);
+    uint64_t* out = reinterpret_cast<uint64_t*>(dst + vb.first);
+    for (uint32_t k = threadIdx.x; k < vb.n; k += blockDim.x) out[k] = src[k];
+}
+
+// ... and the pass's tile order: dst[pos] = the tile of position pos (P->vorder, or pos itself),
+// or -1 when that tile's view is not selected (or the position holds no tile of the frame).  A
+// selected tile keeps its slot, so the packed sums never move.  view_h: the rows of one view, a
+// multiple of tile_h.
+__global__ void gs_views_order_kernel(const KParams* __restrict__ P, int32_t* __restrict__ dst, uint32_t n_pos,
+                                      uint32_t view_h) {
+    for (uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x; pos < n_pos; pos += gridDim.x * blockDim.x) {
+        const int32_t tile = P->vorder ? P->vorder[pos] : (int32_t)pos;
+        int32_t t = -1;
+        if (tile >= 0) {
+            const uint32_t row = ((uint32_t)tile / (uint32_t)P->tiles_x) * (uint32_t)P->tile_h;
+            if (row < (uint32_t)P->cam.image_height && P->vstate[row / view_h].selected) t = tile;
+        }
+        dst[pos] = t;
+    }
+}
+
+// Progressive views: gs_accumulate_kernel for a pass over a subset of a batch of views.  Block b
+// takes tile slot b of this rank (its tile from P->vorder: P->order has the unselected views'
+// tiles emptied), which lies in one view v.  A selected view's pixel takes exactly the accumulate
+// kernel's additions -- the pass's chunk sums in chunk order, the tail's 1-sample sums re-formed
+// into chunks of P->chunk first -- and resolves to sums / (double)(before + batch); an unselected
+// view's pixel resolves again from its stored sums, sums / (double)before (0 while the view has
+// no samples), so a buffer never seen before is filled whole.  The pass's change: each thread adds
+// its pixels' terms in pixel order, the block folds its 256 values through LDS in a fixed tree
+// and writes vdelta[b]: one partial per slot, a function of the capacity and the tile size alone.
+__global__ __launch_bounds__(256) void gs_views_accumulate_kernel(const KParams* __restrict__ P) {
+    __shared__ double s_red[256];
+    const uint32_t tile_px = (uint32_t)(P->tile_w * P->tile_h);
+    const uint32_t slot = blockIdx.x;
+    const uint32_t pos = (uint32_t)P->rank + slot * (uint32_t)P->world_size;
+    const uint32_t tile = P->vorder ? (uint32_t)P->vorder[pos] : pos;  // -1: empty slot
+    const uint32_t W = (uint32_t)P->cam.image_width, H = (uint32_t)P->cam.image_height;
+    const uint32_t x0 = (tile % (uint32_t)P->tiles_x) * (uint32_t)P->tile_w;
+    const uint32_t y0 = (tile / (uint32_t)P->tiles_x) * (uint32_t)P->tile_h;
+    const bool tile_real = tile != 0xFFFFFFFFu && y0 < H;
+    GsViewState vs{0u, 0u};
+    if (tile_real) vs = P->vstate[udiv(y0 * W, P->u_vpx)];
+    const uint32_t cpp = P->cpp, bs = P->ss.batch_size;
+    const uint32_t n_after_u = vs.selected ? vs.before + bs : vs.before;
+    const double n_before = (double)vs.before, n_after = (double)n_after_u;
+    double change = 0.0;
+    for (uint32_t w = threadIdx.x; w < tile_px; w += blockDim.x) {
+        const uint32_t k = slot * tile_px + w;
+        const uint32_t pi = x0 + w % (uint32_t)P->tile_w, pj = y0 + w / (uint32_t)P->tile_w;
+        const bool real = tile_real && pi < W && pj < H;
+        const size_t oi = P->direct ? (size_t)pj * W + pi : (size_t)k;
+        float* o = P->out ? P->out + oi * 3 : nullptr;
+        uint8_t* o8 = P->out8 ? P->out8 + oi * 3 : nullptr;
+        double cr = 0.0, cg = 0.0, cb = 0.0;
+        if (!real) {
+            if (P->direct) continue;
+        } else {
+            double* acc = P->accum + (size_t)k * 3;
+            const double r0 = acc[0], g0 = acc[1], b0 = acc[2];
+            double r = r0, g = g0, b = b0;
+            if (vs.selected) {
+                const bool fine = k >= P->fine_px;
+                // chunk-major sums: consecutive lanes read consecutive 24-B sums of each chunk
+                const size_t stride = (size_t)(fine ? P->capacity - P->fine_px : P->fine_px) * 3;
+                const double* p = P->partial + (fine ? (size_t)P->fine_base + (k - P->fine_px) : (size_t)k) * 3;
+                if (!fine) {
+                    for (uint32_t c = 0; c < cpp; c++, p += stride) {
+                        r += p[0];
+                        g += p[1];
+                        b += p[2];
+                    }
+                } else {
+                    const uint32_t c = P->chunk;  // (bs is a multiple of c)
+                    for (uint32_t s0 = 0; s0 < bs; s0 += c) {
+                        const uint32_t e = min(bs, s0 + c);
+                        double sr = 0.0, sg = 0.0, sb = 0.0;
+                        for (uint32_t s = s0; s < e; s++, p += stride) {
+                            sr += p[0];
+                            sg += p[1];
+                            sb += p[2];
+                        }
+                        r += sr;
+                        g += sg;
+                        b += sb;
+                    }
+                }
+                acc[0] = r;
+                acc[1] = g;
+                acc[2] = b;
+            }
+            if (n_after_u) {
+                cr = r / n_after;
+                cg = g / n_after;
+                cb = b / n_after;
+            }
+            if (vs.selected) {
+                const double pr = vs.before ? r0 / n_before : 0.0, pg = vs.before ? g0 / n_before : 0.0,
+                             pb = vs.before ? b0 / n_before : 0.0;
+                change += fabs(cr - pr);
+                change += fabs(cg - pg);
+                change += fabs(cb - pb);
+            }
+        }
+        if (o) {
+            o[0] = (float)cr;
+            o[1] = (float)cg;
+            o[2] = (float)cb;
+        }
+        if (o8) {
+            o8[0] = color_byte(cr);
+            o8[1] = color_byte(cg);
+            o8[2] = color_byte(cb);
+        }
+    }
+    s_red[threadIdx.x] = change;
+    __syncthreads();
+    for (uint32_t h = 128; h > 0; h >>= 1) {
+        if (threadIdx.x < h) s_red[threadIdx.x] += s_red[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && P->vdelta) P->vdelta[slot] = s_red[0];
+}
+
 // ------------------------------------------------ adaptive sampling in batch rounds
 // The reference's adaptive loop (camera.rs:135-165) runs a pixel's batches one after the
 // other, each batch's stop test over the running sums.  Per-lane that puts up to
@@ -2906,6 +3033,19 @@ hipError_t launch_combine_kernel(hipStream_t st, unsigned grid, const KParams* P
 }
 hipError_t launch_accumulate_kernel(hipStream_t st, const KParams* P, uint32_t capacity) {
     hipLaunchKernelGGL(gs_accumulate_kernel, dim3(gs_accum_blocks(capacity)), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+hipError_t launch_view_state_kernel(hipStream_t st, const ViewStateBatch& vb, GsViewState* dst) {
+    hipLaunchKernelGGL(gs_view_state_kernel, dim3(1), dim3(64), 0, st, vb, dst);
+    return hipGetLastError();
+}
+hipError_t launch_views_order_kernel(hipStream_t st, const KParams* P, int32_t* dst, uint32_t n_pos, uint32_t view_h) {
+    const unsigned grid = (unsigned)((n_pos - 1u) / 256u + 1u < 1024u ? (n_pos - 1u) / 256u + 1u : 1024u);
+    hipLaunchKernelGGL(gs_views_order_kernel, dim3(grid), dim3(256), 0, st, P, dst, n_pos, view_h);
+    return hipGetLastError();
+}
+hipError_t launch_views_accumulate_kernel(hipStream_t st, const KParams* P, uint32_t slots) {
+    hipLaunchKernelGGL(gs_views_accumulate_kernel, dim3(slots), dim3(256), 0, st, P);
     return hipGetLastError();
 }
 hipError_t launch_round_init_kernel(hipStream_t st, unsigned grid, const KParams* P) {

@@ -34,6 +34,17 @@ gs_status gs_render_tiles_views_timed_async(const gs_device_scene* ds, const gs_
                                             uint32_t samples, uint32_t chunk, const gs_partition* part,
                                             const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
                                             hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters);
+// gs_render_tiles_views_pass_async with the same extras.
+gs_status gs_render_tiles_views_pass_timed_async(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                                 const uint32_t* view_samples, const uint8_t* selected, uint32_t samples,
+                                                 uint32_t chunk, const gs_partition* part, double* d_sums,
+                                                 const gs_render_outputs* outs, double* d_delta_partials,
+                                                 gs_counters* d_counters, void* stream, hipEvent_t k_begin,
+                                                 hipEvent_t k_end, bool direct, bool zero_counters);
+// The checks of a views pass's selection (all on the arguments alone): view_samples whole chunks
+// of c, a selection (NULL: every view) that is not empty and whose views hold one count, *base.
+gs_status gs_views_pass_check(uint32_t n_views, const uint32_t* view_samples, const uint8_t* selected, uint32_t samples,
+                              uint32_t c, uint32_t* base);
 // The checks of a views call that need no partition (all on the arguments alone), and the tall
 // frame's camera: view 0's with image_height = V H.  c: the chunk, resolved (never 0).
 gs_status gs_views_check(const gs_device_scene* ds, const gs_view* views, uint32_t n_views, uint32_t samples, uint32_t c,

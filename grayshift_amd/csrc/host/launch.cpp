@@ -232,6 +232,10 @@ struct RoundArgs {
 struct ViewsArgs {
     const gs_view* views;
     uint32_t n, chunk;
+    // A progressive views pass (gs_render_tiles_views_pass_async; with PassArgs): the per-view
+    // records (host, n of them; null for a plain views launch) and the per-slot change partials.
+    const GsViewState* vstate = nullptr;
+    double* d_vdelta = nullptr;
 };
 static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                         const gs_partition* part, const gs_render_outputs* outs, gs_counters* d_counters, void* stream,
@@ -356,6 +360,78 @@ extern "C" gs_status gs_render_tiles_views_async(const gs_device_scene* ds, cons
                                                  const gs_render_outputs* outs, gs_counters* d_counters, void* stream) {
     return gs_render_tiles_views_timed_async(ds, views, n_views, samples, chunk, part, outs, d_counters, stream, nullptr,
                                              nullptr, false, false);
+}
+
+// ---------------------------------------------------------------- progressive views
+extern "C" int32_t gs_views_tile_h(int32_t height, int32_t tile_h) {
+    if (height <= 0 || tile_h <= 0) return 0;
+    int32_t t = std::min(height, tile_h);
+    while (height % t != 0) t--;
+    return t;
+}
+
+// The checks of a views pass's selection, on the arguments alone: the selected views' common
+// sample count into *base.  selected NULL: every view.
+gs_status gs_views_pass_check(uint32_t n_views, const uint32_t* view_samples, const uint8_t* selected, uint32_t samples,
+                              uint32_t c, uint32_t* base) {
+    if (!view_samples || !base) return fail(GS_ERR_ARG, "null argument");
+    bool any = false;
+    uint32_t b = 0;
+    for (uint32_t v = 0; v < n_views; v++) {
+        if (view_samples[v] % c != 0)
+            return fail(GS_ERR_ARG, "view " + std::to_string(v) + "'s samples are not a multiple of the chunk");
+        if (selected && !selected[v]) continue;
+        if (any && view_samples[v] != b)
+            return fail(GS_ERR_ARG, "the selected views hold different sample counts (view " + std::to_string(v) +
+                                        "): one pass per count");
+        b = view_samples[v];
+        any = true;
+    }
+    if (!any) return fail(GS_ERR_ARG, "an empty selection: no view to render");
+    if ((uint64_t)b + samples > 0xFFFFFFFFull) return fail(GS_ERR_ARG, "a view's samples overflow 32 bits");
+    *base = b;
+    return GS_OK;
+}
+
+gs_status gs_render_tiles_views_pass_timed_async(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                                 const uint32_t* view_samples, const uint8_t* selected, uint32_t samples,
+                                                 uint32_t chunk, const gs_partition* part, double* d_sums,
+                                                 const gs_render_outputs* outs, double* d_delta_partials,
+                                                 gs_counters* d_counters, void* stream, hipEvent_t k_begin,
+                                                 hipEvent_t k_end, bool direct, bool zero_counters) {
+    const uint32_t c = chunk ? chunk : 16u;
+    gs_camera tall;
+    gs_status e = gs_views_check(ds, views, n_views, samples, c, &tall);
+    if (e != GS_OK) return e;
+    if (!d_sums) return fail(GS_ERR_ARG, "null argument");
+    uint32_t base = 0;
+    e = gs_views_pass_check(n_views, view_samples, selected, samples, c, &base);
+    if (e == GS_OK) e = check_views_part(tall, part, samples, c, outs);
+    if (e != GS_OK) return e;
+    if (views[0].cam.image_height % part->tile_h != 0)
+        return fail(GS_ERR_ARG, "tile_h does not divide the views' height (gs_views_tile_h): a tile would straddle two views");
+    if (!has_views(ds->feat))
+        return fail(GS_ERR_UNSUPPORTED, "the scene needs the catch-all kernel, which has no views form");
+    const gs_sample_settings ss{0.0, 0.0, samples, 0};  // one batch of `samples` (max_samples < batch_size)
+    e = ensure_placement(const_cast<gs_device_scene*>(ds), &views[0].cam, &ss, stream);  // (view 0's own frame)
+    if (e != GS_OK) return e;
+    std::vector<GsViewState> vs(n_views);
+    for (uint32_t v = 0; v < n_views; v++) vs[v] = GsViewState{view_samples[v], (!selected || selected[v]) ? 1u : 0u};
+    const PassArgs pa{base, c, d_sums, nullptr};
+    ViewsArgs vw{views, n_views, c};
+    vw.vstate = vs.data();
+    vw.d_vdelta = d_delta_partials;
+    return launch(ds, &tall, &ss, 0, part, outs, d_counters, stream, k_begin, k_end, nullptr, direct, zero_counters, &pa,
+                  nullptr, &vw);
+}
+
+extern "C" gs_status gs_render_tiles_views_pass_async(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                                      const uint32_t* view_samples, const uint8_t* selected,
+                                                      uint32_t samples, uint32_t chunk, const gs_partition* part,
+                                                      double* d_sums, const gs_render_outputs* outs,
+                                                      double* d_delta_partials, gs_counters* d_counters, void* stream) {
+    return gs_render_tiles_views_pass_timed_async(ds, views, n_views, view_samples, selected, samples, chunk, part, d_sums,
+                                                  outs, d_delta_partials, d_counters, stream, nullptr, nullptr, false, false);
 }
 
 // ---------------------------------------------------------------- progressive adaptive passes
@@ -897,7 +973,9 @@ static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const Launch
                                     : q.feat | (fixed ? GS_FEAT_FIXED : 0);
     HIPCHK(launch_render_kernel(q.st, q.kernel(feat), q.blocks, q.lds, a));
     if (q.k_end) HIPCHK(hipEventRecord(q.k_end, q.st));
-    if (pass) {  // (always chunked: the pass's sums join the frame's)
+    if (pass && views) {  // (a progressive views pass: one block per tile slot)
+        HIPCHK(launch_views_accumulate_kernel(q.st, dP, r.cap / (uint32_t)(r.part->tile_w * r.part->tile_h)));
+    } else if (pass) {  // (always chunked: the pass's sums join the frame's)
         HIPCHK(launch_accumulate_kernel(q.st, dP, r.cap));
     } else if (w.chunk) {
         const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)r.cap + 255) / 256, 8192);
@@ -1014,10 +1092,30 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
         kp.views = sl.views;
         kp.u_vpx = gsd::udiv_make((uint32_t)cam->image_width * (uint32_t)vw->views[0].cam.image_height);
     }
+    // (a progressive views pass: the per-view records likewise, and room for the pass's own tile
+    // order, which gs_views_order_kernel writes behind the parameter kernel)
+    const uint32_t vp_pos = vw && vw->vstate ? req.cap / (uint32_t)(part->tile_w * part->tile_h) * (uint32_t)part->world_size : 0u;
+    if (vp_pos) {
+        e = grow_buffer(sl, sl.vstate, sl.vstate_bytes, (size_t)vw->n * sizeof(GsViewState), "view states");
+        if (e == GS_OK) e = grow_buffer(sl, sl.vorder, sl.vorder_bytes, (size_t)vp_pos * sizeof(int32_t), "the pass's tile order");
+        if (e != GS_OK) return e;
+        for (uint32_t first = 0; first < vw->n; first += GS_VSTATE_BATCH) {
+            ViewStateBatch vb{};
+            vb.first = first;
+            vb.n = std::min<uint32_t>(GS_VSTATE_BATCH, vw->n - first);
+            std::memcpy(vb.s, vw->vstate + first, (size_t)vb.n * sizeof(GsViewState));
+            HIPCHK(launch_view_state_kernel(st, vb, sl.vstate));
+        }
+        kp.vstate = sl.vstate;
+        kp.vorder = part->d_tile_order;
+        kp.order = sl.vorder;
+        kp.vdelta = vw->d_vdelta;
+    }
     KArgs a = fill_args(ds, lc, chunked, k);
     a.P = sl.params;
     if (outs->item_visits) HIPCHK(hipMemsetAsync(outs->item_visits, 0, (size_t)cap * sizeof(uint32_t), st));
     HIPCHK(launch_params_kernel(st, kp, sl.params));  // (zeroes the queue)
+    if (vp_pos) HIPCHK(launch_views_order_kernel(st, sl.params, sl.vorder, vp_pos, (uint32_t)vw->views[0].cam.image_height));
     const Enqueue q{st, (unsigned)blocks, lc.lds, lc.feat, k_begin, k_end, ds};
     e = ra ? enqueue_round_pass(q, w, k, req, *ra, kp, sl.params, a)
         : w.n_rounds ? enqueue_rounds(q, w, k, req, kp, sl.params, a)

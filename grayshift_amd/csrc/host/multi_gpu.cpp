@@ -211,6 +211,19 @@ struct gs_multi {
     // ad_base (an upload's) + ad_dev.
     bool ad_fresh = true;
     gs_counters ad_counters{}, ad_base{}, ad_dev{};
+    // The open views accumulation (gs_multi_views_accum_begin .. _end): the views and the chunk are
+    // fixed, the tall frame is cut round-robin into tw x va_th tiles (`th` holds va_th while it is
+    // open, th_ctx the context's own), view v's sums hold va_samples[v] samples.  The ranks' sums
+    // and change partials are the accumulation's buffers (Device::sums, delta: one per tile slot),
+    // acc_cam the tall frame's camera (permute_sums).
+    bool va_open = false;
+    int32_t th_ctx = 64;
+    std::vector<gs_view> va_views;
+    gs_camera va_tall{};
+    uint32_t va_chunk = 0, va_passes = 0;
+    std::vector<uint32_t> va_samples;
+    std::vector<double> va_delta;
+    gs_counters va_counters{};
 
     ~gs_multi() {
         DeviceGuard g;
@@ -268,9 +281,17 @@ struct gs_multi {
         const gs_view* views;
         uint32_t n, chunk;
     };
+    // vp: a pass of the open views accumulation (with vw: its views), over the views `selected`
+    // (NULL: all), which all hold `base` samples
+    struct ViewsPass {
+        const uint8_t* selected;
+        uint32_t base;
+    };
     gs_status render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, const gs_multi_outputs* out,
                      gs_stats* stats, uint32_t pass_samples = 0, bool adapt = false, uint32_t adapt_rounds = 0,
-                     const ViewsCall* vw = nullptr);
+                     const ViewsCall* vw = nullptr, const ViewsPass* vp = nullptr);
+    gs_status views_accum_begin(const gs_view* views, uint32_t n_views, uint32_t chunk);
+    void views_accum_end();
     gs_status accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk);
     void accum_end();
     // The tile (or -1) of rank `rank`'s slot `slot`, and the slots the rank holds.
@@ -328,7 +349,7 @@ gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_
 
 gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                            const gs_multi_outputs* out, gs_stats* stats, uint32_t pass_samples, bool adapt,
-                           uint32_t adapt_rounds, const ViewsCall* vw) {
+                           uint32_t adapt_rounds, const ViewsCall* vw, const ViewsPass* vp) {
     if (!cam || !ss) return fail(GS_ERR_ARG, "null argument");
     if (out && !out->rgb && !out->rgb8 && !out->ppm_text) return fail(GS_ERR_ARG, "no output requested");
     if (out && out->ppm_text && !out->ppm_len) return fail(GS_ERR_ARG, "ppm_text without ppm_len");
@@ -340,6 +361,8 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
     if (ad_open && !adapt)  // (likewise: the round state is in the plan's packed order)
         return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
+    if (va_open && !vp)  // (likewise: the views' sums are in the packed order of its own tile height)
+        return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
     DeviceGuard guard;
     const auto t0 = std::chrono::steady_clock::now();
     const int n = (int)dev.size();
@@ -393,6 +416,11 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
             s = gs_render_tiles_pass_timed_async(d.scene, cam, pass_samples, seed, &p, (uint32_t)acc_samples, acc_chunk,
                                                  (double*)d.sums.p, (double*)d.delta.p, &o, (gs_counters*)d.cnt.p,
                                                  d.stream, d.ev[2], d.ev[3], direct, true);
+        } else if (vp) {  // (every slot's partial is written by the pass's combine: no memset)
+            s = gs_render_tiles_views_pass_timed_async(d.scene, vw->views, vw->n, va_samples.data(), vp->selected,
+                                                       ss->batch_size, vw->chunk, &p, (double*)d.sums.p, &o,
+                                                       (double*)d.delta.p, (gs_counters*)d.cnt.p, d.stream, d.ev[2],
+                                                       d.ev[3], direct, true);
         } else if (vw) {
             s = gs_render_tiles_views_timed_async(d.scene, vw->views, vw->n, ss->batch_size, vw->chunk, &p, &o,
                                                   (gs_counters*)d.cnt.p, d.stream, d.ev[2], d.ev[3], direct, true);
@@ -487,6 +515,9 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         if (pass_samples)
             HIPOK(hipMemcpyAsync(d.h_delta, d.delta.p, (size_t)gs_pass_delta_blocks(cap) * 8, hipMemcpyDeviceToHost,
                                  d.stream));
+        if (vp)
+            HIPOK(hipMemcpyAsync(d.h_delta, d.delta.p, (size_t)(cap / ((int64_t)tw * th)) * 8, hipMemcpyDeviceToHost,
+                                 d.stream));
     }
     // Wait, then results.
     gs_counters total{};
@@ -535,6 +566,30 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         add_counters(acc_counters, add);
         acc_samples += pass_samples;
         acc_passes += 1;
+    }
+    if (vp) {
+        // the selected views' change: a view's per-slot partials rank after rank, each rank's in
+        // slot order (round-robin: rank i's slot sl holds tile i + sl n, which lies in one view)
+        const int64_t vh = va_views[0].cam.image_height, tx = (W + tw - 1) / tw, nt = tx * (H / th);
+        std::vector<double> change(vw->n, 0.0);
+        for (int i = 0; i < n; i++) {
+            const int64_t ns = rank_cap(i, *cam) / ((int64_t)tw * th);
+            for (int64_t sl = 0; sl < ns; sl++) {
+                const int64_t tile = i + sl * n;
+                if (tile < nt) change[(size_t)((tile / tx) * th / vh)] += dev[i].h_delta[sl];
+            }
+        }
+        for (uint32_t v = 0; v < vw->n; v++)
+            if (!vp->selected || vp->selected[v]) {
+                va_delta[v] = change[v] / ((double)W * (double)vh * 3.0);
+                va_samples[v] += ss->batch_size;
+            }
+        gs_counters add = total;
+        // (the kernel counts the selected views' pixels at chunk 0 of every pass; they all start
+        // at sample 0 or none does)
+        if (vp->base != 0) add.pixels = 0;
+        add_counters(va_counters, add);
+        va_passes += 1;
     }
     if (adapt) {
         ad_active = ad_samples_total = ad_samples_max = 0;
@@ -588,6 +643,7 @@ int32_t gs_multi::slot_tile(int rank, int64_t slot) const {
 gs_status gs_multi::accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk) {
     if (acc_open) return fail(GS_ERR_ARG, "an accumulation is already open: gs_multi_accum_end first");
     if (ad_open) return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
+    if (va_open) return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
     if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
     DeviceGuard guard;
@@ -666,10 +722,80 @@ gs_status gs_multi::permute_sums(double* image, bool to_image) {
     return GS_OK;
 }
 
+// ---------------------------------------------------------------- progressive views
+// (the arguments are checked by the caller: gs_views_check)
+gs_status gs_multi::views_accum_begin(const gs_view* views, uint32_t n_views, uint32_t chunk) {
+    if (va_open) return fail(GS_ERR_ARG, "a views accumulation is already open: gs_multi_views_accum_end first");
+    if (acc_open) return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
+    if (ad_open) return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
+    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
+    gs_scene_info si{};
+    gs_status s = gs_device_scene_info(dev[0].scene, &si);
+    if (s != GS_OK) return s;
+    if (si.feat & 512)
+        return fail(GS_ERR_UNSUPPORTED, "the scene needs the catch-all kernel, which has no views form");
+    gs_camera tall = views[0].cam;
+    tall.image_height = (int32_t)(n_views * (uint32_t)views[0].cam.image_height);
+    DeviceGuard guard;
+    // the accumulation's own tile height, so that no tile straddles two views; the cut is redone
+    // whatever camera the last frame had (the partition's cache does not know the tile height)
+    th_ctx = th;
+    th = gs_views_tile_h(views[0].cam.image_height, th_ctx);
+    part_ready = false;
+    double plan_ms = 0.0;
+    s = partition(&tall, 0, &plan_ms, true);
+    if (s == GS_OK && (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll)) s = fail(GS_ERR_ARG, "bad partition");
+    const size_t nb = s == GS_OK ? (size_t)(cap / ((int64_t)tw * th)) : 0;
+    for (size_t i = 0; s == GS_OK && i < dev.size(); i++) {
+        Device& d = dev[i];
+        if (hipSetDevice(d.id) != hipSuccess || !d.sums.ensure((size_t)cap * 24) || !d.delta.ensure(nb * 8)) {
+            s = fail(GS_ERR_OOM, "hipMalloc of the views' sums failed");
+            break;
+        }
+        if (d.h_delta) (void)hipHostFree(d.h_delta);
+        d.h_delta = nullptr;
+        if (hipHostMalloc((void**)&d.h_delta, nb * 8, hipHostMallocDefault) != hipSuccess)
+            s = fail(GS_ERR_OOM, "hipHostMalloc of the pass's change failed");
+        else if (hipMemsetAsync(d.sums.p, 0, (size_t)cap * 24, d.stream) != hipSuccess ||
+                 hipStreamSynchronize(d.stream) != hipSuccess)
+            s = fail(GS_ERR_HIP, "zeroing the views' sums failed");
+    }
+    va_open = true;  // (views_accum_end undoes a partial begin)
+    if (s != GS_OK) {
+        views_accum_end();
+        return s;
+    }
+    va_views.assign(views, views + n_views);
+    va_tall = tall;
+    acc_cam = tall;  // (permute_sums, rank_slots)
+    va_chunk = chunk ? chunk : 16u;
+    va_passes = 0;
+    va_samples.assign(n_views, 0u);
+    va_delta.assign(n_views, 0.0);
+    va_counters = gs_counters{};
+    return GS_OK;
+}
+
+void gs_multi::views_accum_end() {
+    DeviceGuard guard;
+    for (auto& d : dev) {
+        (void)hipSetDevice(d.id);
+        if (d.stream && !comms_broken) (void)hipStreamSynchronize(d.stream);
+        d.sums.release();
+        d.delta.release();
+        if (d.h_delta) (void)hipHostFree(d.h_delta);
+        d.h_delta = nullptr;
+    }
+    th = th_ctx;
+    part_ready = false;
+    va_open = false;
+}
+
 // ---------------------------------------------------------------- progressive adaptation
 gs_status gs_multi::adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed) {
     if (ad_open) return fail(GS_ERR_ARG, "an adaptation is already open: gs_multi_adapt_end first");
     if (acc_open) return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
+    if (va_open) return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
     if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
     if (ss->batch_size == 0) return fail(GS_ERR_ARG, "batch_size 0 never terminates (camera.rs:137)");
@@ -1053,6 +1179,95 @@ gs_status gs_multi_render_views(gs_multi* m, const gs_view* views, uint32_t n_vi
     const gs_sample_settings ss{0.0, 0.0, samples, 0};
     const gs_multi::ViewsCall vw{views, n_views, c};
     return m->render(&tall, &ss, 0, out, stats, 0, false, 0, &vw);
+}
+
+// ---- progressive views
+gs_status gs_multi_views_accum_begin(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    const uint32_t c = chunk ? chunk : 16u;
+    gs_camera tall;
+    gs_status s = gs_views_check(m->dev[0].scene, views, n_views, c, c, &tall);  // (one chunk: the views' own rules)
+    if (s != GS_OK) return s;
+    return m->views_accum_begin(views, n_views, chunk);
+}
+
+gs_status gs_multi_views_accum_pass(gs_multi* m, uint32_t samples, const uint8_t* selected, const gs_multi_outputs* out,
+                                    gs_stats* stats) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->va_open) return fail(GS_ERR_ARG, "no views accumulation is open: gs_multi_views_accum_begin first");
+    if (out && out->ppm_text) return fail(GS_ERR_ARG, "a views pass writes no PPM text");
+    const uint32_t c = m->va_chunk, nv = (uint32_t)m->va_views.size();
+    if (samples == 0 || samples % c != 0 || samples / c > 64u)
+        return fail(GS_ERR_ARG, "a pass is 1 to 64 whole chunks of samples");
+    uint32_t base = 0;
+    gs_status s = gs_views_pass_check(nv, m->va_samples.data(), selected, samples, c, &base);
+    if (s != GS_OK) return s;
+    // (rank 0 holds the most tiles of the round-robin cut: its share bounds every rank's)
+    const gs_partition p0{0, (int32_t)m->dev.size(), m->tw, m->th, nullptr, 0, 0};
+    s = gs_views_check_cap(gs_partition_capacity(&m->va_tall, &p0), samples, c);
+    if (s != GS_OK) return s;
+    const gs_sample_settings ss{0.0, 0.0, samples, 0};
+    const gs_multi::ViewsCall vw{m->va_views.data(), nv, c};
+    const gs_multi::ViewsPass vp{selected, base};
+    return m->render(&m->va_tall, &ss, 0, out, stats, 0, false, 0, &vw, &vp);
+}
+
+gs_status gs_multi_views_accum_info(const gs_multi* m, gs_views_accum_info* info, uint32_t* view_samples_out,
+                                    double* delta_out) {
+    if (!m || !info) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->va_open) return fail(GS_ERR_ARG, "no views accumulation is open");
+    std::memset(info, 0, sizeof(*info));
+    info->width = m->va_views[0].cam.image_width;
+    info->height = m->va_views[0].cam.image_height;
+    info->n_views = (uint32_t)m->va_views.size();
+    info->chunk = m->va_chunk;
+    info->passes = m->va_passes;
+    info->tile_h = m->th;
+    info->counters = m->va_counters;
+    if (view_samples_out) std::memcpy(view_samples_out, m->va_samples.data(), m->va_samples.size() * sizeof(uint32_t));
+    if (delta_out) std::memcpy(delta_out, m->va_delta.data(), m->va_delta.size() * sizeof(double));
+    return GS_OK;
+}
+
+gs_status gs_multi_views_accum_download(gs_multi* m, double* sums) {
+    if (!m || !sums) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->va_open) return fail(GS_ERR_ARG, "no views accumulation is open");
+    return m->permute_sums(sums, true);
+}
+
+gs_status gs_multi_views_accum_upload(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk,
+                                      const uint32_t* view_samples, const double* sums, const gs_counters* counters) {
+    if (!m || !view_samples || !sums || !counters) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    const uint32_t c = chunk ? chunk : 16u;
+    gs_camera tall;
+    gs_status s = gs_views_check(m->dev[0].scene, views, n_views, c, c, &tall);
+    if (s != GS_OK) return s;
+    for (uint32_t v = 0; v < n_views; v++)
+        if (view_samples[v] % c != 0)
+            return fail(GS_ERR_ARG, "a checkpoint's samples are whole chunks (view " + std::to_string(v) + ")");
+    s = m->views_accum_begin(views, n_views, chunk);
+    if (s != GS_OK) return s;
+    s = m->permute_sums(const_cast<double*>(sums), false);
+    if (s != GS_OK) {
+        m->views_accum_end();
+        return s;
+    }
+    m->va_samples.assign(view_samples, view_samples + n_views);
+    m->va_counters = *counters;
+    return GS_OK;
+}
+
+gs_status gs_multi_views_accum_end(gs_multi* m) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->va_open) return fail(GS_ERR_ARG, "no views accumulation is open");
+    m->views_accum_end();
+    return GS_OK;
 }
 
 gs_status gs_multi_frame(const gs_multi* m, const float** d_rgb, const uint8_t** d_rgb8, int32_t* device) {

@@ -68,6 +68,11 @@ struct LaunchSlot {
     // a views launch's records (KParams::views)
     gs_view* views = nullptr;
     size_t views_bytes = 0;
+    // a progressive views pass's per-view records (KParams::vstate) and its tile order (KParams::order)
+    GsViewState* vstate = nullptr;
+    size_t vstate_bytes = 0;
+    int32_t* vorder = nullptr;
+    size_t vorder_bytes = 0;
 };
 static const int kLaunchSlots = 4;
 

@@ -1031,6 +1031,8 @@ gs_status gs_device_scene_destroy(gs_device_scene* ds) {
         if (sl.rbuf) (void)hipFree(sl.rbuf);
         if (sl.nest_save) (void)hipFree(sl.nest_save);
         if (sl.views) (void)hipFree(sl.views);
+        if (sl.vstate) (void)hipFree(sl.vstate);
+        if (sl.vorder) (void)hipFree(sl.vorder);
     }
     if (ds->mem) (void)hipFree(ds->mem);
     delete ds;

@@ -7,6 +7,8 @@
   f64 sums: preview, add samples, checkpoint, resume (bit-identical to the one-shot render).
 * ``AdaptiveRenderer`` — the scene's own adaptive SampleSettings in passes of batch rounds:
   preview, per-pixel sample-count and error maps, checkpoint, resume (bit-identical too).
+* ``ViewsProgressiveRenderer`` — a batch of cameras refined in passes, view by view: per-view
+  sample budgets and change, preview, checkpoint, resume (each view bit-identical to its own render).
 * ``Renderer`` — device-resident scene for repeated / multi-GPU rendering: upload once,
   render this rank's tiles into a caller-provided device buffer on a given stream.
   Used by bench.py with torch tensors as the device buffers (torch is plumbing only).
@@ -587,6 +589,249 @@ class AdaptiveRenderer:
         if mr is not None:
             if self._open and mr.handle:
                 N.lib.gs_multi_adapt_end(mr.handle)
+            self._open = False
+            mr.close()
+            self._mr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
+            pass
+
+
+class ViewsProgressiveRenderer:
+    """A batch of cameras of one world refined in passes, view by view (gs_multi_views_accum_*):
+    every pass adds `samples` more samples per pixel to the f64 sums of a subset of the views and
+    returns all V frames resolved so far.
+
+    The contract: after any sequence of passes in which view v received n_v samples, its sums, f32
+    frame and rgb8 frame are bit for bit those of a fixed-spp render of cameras[v] with seed
+    seeds[v], n_v samples and the same chunk (render_views with that one camera;
+    ProgressiveRenderer on it) -- whatever the split into passes, the subset history, the other
+    cameras, the GPU count, the tile size or a save() / resume() in between -- and the cumulative
+    counters are the sums of those V renders' counters: an unselected view costs no ray.
+
+    cameras: gs_camera_specs of one width and height; seeds: one per camera (default 1 each);
+    chunk: the coarse sample chunk c (0 = 16), every pass is 1 to 64 whole chunks.  The scene's own
+    camera and SampleSettings are not used."""
+
+    def __init__(self, scene, cameras, seeds=None, num_gpus=1, chunk=0, tile=64, devices=None, _resume=None):
+        self.scene = scene
+        self._cams = [camera(c) for c in cameras]
+        V = len(self._cams)
+        self.seeds = [1] * V if seeds is None else [int(s) for s in seeds]
+        if len(self.seeds) != V:
+            raise ValueError("one seed per camera")
+        self._views = (N.gs_view * max(V, 1))()
+        for v in range(V):
+            self._views[v].cam = self._cams[v]
+            self._views[v].seed = self.seeds[v]
+        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices)
+        self._open = False
+        self._passes0 = 0
+        self._deltas0 = None
+        try:
+            if _resume is None:
+                N.check(N.lib.gs_multi_views_accum_begin(self._mr.handle, self._views, V, int(chunk)))
+            else:
+                sums, meta = _resume
+                cnt = N.gs_counters(**meta["counters"])
+                ns = np.array(meta["samples"], dtype=np.uint32)
+                N.check(N.lib.gs_multi_views_accum_upload(self._mr.handle, self._views, V, int(chunk), ns.ctypes.data,
+                                                          sums.ctypes.data, C.byref(cnt)))
+                self._passes0 = meta.get("passes", 0)
+                self._deltas0 = np.array(meta.get("deltas", [0.0] * V), dtype=np.float64)
+            self._open = True
+            i = self._info()[0]
+            self.chunk, self.n_views, self.width, self.height = i.chunk, i.n_views, i.width, i.height
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def devices(self):
+        return self._mr.devices
+
+    def _info(self):
+        i = N.gs_views_accum_info()
+        V = len(self._cams)
+        ns = np.zeros(max(V, 1), dtype=np.uint32)
+        ds = np.zeros(max(V, 1), dtype=np.float64)
+        N.check(N.lib.gs_multi_views_accum_info(self._mr.handle, C.byref(i), ns.ctypes.data, ds.ctypes.data))
+        if self._deltas0 is not None:  # (after resume(): a view's checkpointed delta until a pass selects it)
+            ds = np.where(self._fresh, self._deltas0, ds[:V])
+        return i, ns[:V], ds[:V]
+
+    _fresh = True  # (an array of V flags after resume(): views no pass has selected since)
+
+    @property
+    def samples(self):
+        """[V] u32: the samples per pixel accumulated in each view."""
+        return self._info()[1]
+
+    @property
+    def deltas(self):
+        """[V] f64: per view, the mean |change| of the f64 colour over its W*H*3 values in the last
+        pass that selected it (0 before its first)."""
+        return self._info()[2]
+
+    @property
+    def info(self):
+        """width, height (of one view), n_views, chunk, passes, tile_h, the cumulative counters,
+        "samples" and "deltas" (lists, per view).  After resume(), passes continues the
+        checkpoint's count."""
+        i, ns, ds = self._info()
+        d = i.as_dict()
+        d["passes"] += self._passes0
+        d["samples"] = [int(n) for n in ns]
+        d["deltas"] = [float(x) for x in ds]
+        return d
+
+    def _selection(self, views):
+        V = len(self._cams)
+        if views is None:
+            return None, list(range(V))
+        idx = sorted({int(v) for v in views})
+        if any(v < 0 or v >= V for v in idx):
+            raise ValueError("view index out of range")
+        sel = np.zeros(max(V, 1), dtype=np.uint8)
+        sel[idx] = 1
+        return sel, idx
+
+    def render_pass(self, samples, views=None, rgb=True, rgb8=False):
+        """Render `samples` more samples (1 to 64 whole chunks) of every pixel of the views `views`
+        (indices; None: all) and resolve all V frames.  Selected views that hold different sample
+        counts are rendered count by count, one launch each (the library's pass takes one sample
+        base).  Returns a dict: the requested outputs ("rgb" [V,H,W,3] f32, "rgb8"; with none the
+        f32 frames stay on the first device, frame_ptr()), this pass's "counters" and "stats" (a
+        list when it took several launches), and "info" (info after the pass)."""
+        sel, idx = self._selection(views)
+        V, W, H = len(self._cams), self.width, self.height
+        groups = [sel]
+        if sel is not None:
+            ns = self.samples
+            groups = []
+            for n in sorted({int(ns[v]) for v in idx}):
+                g = np.zeros(max(V, 1), dtype=np.uint8)
+                g[[v for v in idx if int(ns[v]) == n]] = 1
+                groups.append(g)
+            if not groups:
+                groups = [sel]  # (empty: the library reports it)
+        elif len({int(n) for n in self.samples}) > 1:
+            return self.render_pass(samples, range(V), rgb, rgb8)
+        res, stats, counters = {}, [], None
+        for k, g in enumerate(groups):
+            last = k == len(groups) - 1
+            out, res, _ = _outputs(W, V * H, rgb and last, rgb8 and last, False)
+            if not last:  # (frames of an intermediate launch stay on the device)
+                out = None
+            st = N.gs_stats()
+            N.check(N.lib.gs_multi_views_accum_pass(self._mr.handle, int(samples), g.ctypes.data if g is not None else None,
+                                                    C.byref(out) if out is not None else None, C.byref(st)))
+            if self._deltas0 is not None:
+                self._fresh = np.where(g[:V] != 0, False, self._fresh) if g is not None else np.zeros(V, dtype=bool)
+            c = st.counters.as_dict()
+            counters = c if counters is None else {n: counters[n] + c[n] for n in c}
+            stats.append({n: v for n, v in st.as_dict().items() if n != "counters"})
+        for k in ("rgb", "rgb8"):
+            if k in res:
+                res[k] = res[k].reshape(V, H, W, 3)
+        res["counters"] = counters
+        res["stats"] = stats if len(stats) > 1 else stats[0]
+        res["info"] = self.info
+        return res
+
+    def render_until(self, total_samples=None, seconds=None, min_delta=None, pass_samples=None, on_pass=None):
+        """Run passes until the first bound is reached: every view still selected holds
+        `total_samples` samples (a multiple of the chunk), or `seconds` of wall time have passed
+        since the call.  With `min_delta`, a view leaves the selection once a pass left its delta
+        below the threshold, and the loop also ends when no view is left.  pass_samples: samples
+        per pass, rounded up to whole chunks and capped at 64 chunks (default: 4 chunks).
+        on_pass(info, frames) is called after every pass with info and the resolved [V,H,W,3] f32
+        frames.  Returns (info, frames) of the last pass; frames is None when no pass ran."""
+        if total_samples is None and seconds is None and min_delta is None:
+            raise ValueError("render_until needs a bound: total_samples, seconds or min_delta")
+        c = self.chunk
+        if total_samples is not None and total_samples % c:
+            raise ValueError("total_samples %d is not a multiple of the chunk %d" % (total_samples, c))
+        step = 4 * c if pass_samples is None else int(pass_samples)
+        step = min(64 * c, max(c, (step + c - 1) // c * c))
+        t0 = time.monotonic()
+        info, frames = self.info, None
+        active = list(range(len(self._cams)))
+        while active:
+            if total_samples is not None:
+                active = [v for v in active if info["samples"][v] < total_samples]
+                if not active:
+                    break
+            if seconds is not None and frames is not None and time.monotonic() - t0 >= seconds:
+                break
+            # (views short of the budget by less than a step take what remains, in a pass of their own)
+            if total_samples is not None:
+                n = min(step, min(total_samples - info["samples"][v] for v in active))
+                now = [v for v in active if total_samples - info["samples"][v] >= n]
+            else:
+                n, now = step, active
+            res = self.render_pass(n, now)
+            info, frames = res["info"], res["rgb"]
+            if on_pass is not None:
+                on_pass(info, frames)
+            if min_delta is not None:
+                active = [v for v in active if v not in now or info["deltas"][v] >= min_delta]
+        return info, frames
+
+    def sums(self):
+        """The running sums, [V, H, W, 3] f64 in image order (a copy on the host)."""
+        out = np.zeros((len(self._cams), self.height, self.width, 3), dtype=np.float64)
+        N.check(N.lib.gs_multi_views_accum_download(self._mr.handle, out.ctypes.data))
+        return out
+
+    def frame_ptr(self):
+        """(device pointer of the last resolved [V,H,W,3] f32 frames or None, its device id)."""
+        return self._mr.frame_ptr()
+
+    def scene_info(self, rank=0):
+        return self._mr.scene_info(rank)
+
+    def save(self, path):
+        """Write a checkpoint (grayshift_amd.checkpoint, format 3): the sums, the per-view samples,
+        seeds and gs_camera bytes, chunk, view size and the cumulative counters."""
+        i = self.info
+        meta = {k: i[k] for k in ("samples", "chunk", "width", "height", "counters", "passes", "deltas")}
+        meta["seeds"] = self.seeds
+        meta["cameras"] = [bytes(c) for c in self._cams]
+        checkpoint.write_views_checkpoint(path, self.sums(), meta)
+
+    @classmethod
+    def resume(cls, scene, path, cameras, seeds=None, **kw):
+        """Continue the checkpoint at `path` on `scene` with the batch `cameras`: **kw as for the
+        constructor (any device count or tile size).  seeds and chunk default to the checkpoint's;
+        the checkpoint is rejected (checkpoint.CheckpointError) when its view count, view size,
+        chunk, seeds or gs_camera bytes differ from the batch's and the ones given.  Whether
+        `scene` is otherwise the world the checkpoint was rendered from is the caller's
+        responsibility."""
+        sums, meta = checkpoint.read_views_checkpoint(path)
+        cams = [camera(c) for c in cameras]
+        seeds = meta["seeds"] if seeds is None else list(seeds)
+        chunk = kw.pop("chunk", meta["chunk"]) or 16
+        W, H = (cams[0].image_width, cams[0].image_height) if cams else (0, 0)
+        checkpoint.check_views_compatible(meta, W, H, chunk, seeds, [bytes(c) for c in cams])
+        r = cls(scene, cameras, seeds=seeds, chunk=chunk, _resume=(sums, meta), **kw)
+        r._fresh = np.ones(len(cams), dtype=bool)
+        return r
+
+    def close(self):
+        mr = getattr(self, "_mr", None)
+        if mr is not None:
+            if self._open and mr.handle:
+                N.lib.gs_multi_views_accum_end(mr.handle)
             self._open = False
             mr.close()
             self._mr = None

@@ -672,7 +672,8 @@ gs_status gs_multi_adapt_end(gs_multi* m);
  * the size: lanes of one wave may hold different views, with and without defocus, of different
  * max_depth.
  *
- * Fixed spp only (no adaptive settings, progressive passes or PPM text over views).  A scene that
+ * Fixed spp only (no adaptive settings or PPM text over views; progressive passes over views,
+ * view by view, are "Progressive views" below).  A scene that
  * needs the catch-all kernel (compositions beyond the reference scenes': gs_scene_info.feat & 512)
  * returns GS_ERR_UNSUPPORTED: that kernel has no views form.
  *
@@ -715,6 +716,99 @@ gs_status gs_multi_render_views(gs_multi* m, const gs_view* views, uint32_t n_vi
  * media, no BVHs under instances, no staged shading: feat & 19 == 0).  0: bad arguments.  A chunk that does not divide `samples` is
  * the one-shot render's all the same, but a views call refuses it. */
 uint32_t gs_views_chunk(const gs_device_scene* scene, const gs_camera* cam, uint32_t samples);
+
+/* ---- Progressive views (additive: the ABI stays 11, no existing call changes) ----
+ * A batch of views accumulated in passes, view by view: V views (all W x H) of one device-resident
+ * scene, the coarse chunk c taken as given (0 = 16).  A pass renders n samples (1 to 64 whole
+ * chunks) of a SUBSET of the views.  After any sequence of passes in which view v received n_v
+ * samples in total:
+ *  1. Frames.  View v's f64 sums, f32 frame and rgb8 frame are, bit for bit, those of a one-shot
+ *     fixed-spp render of views[v].cam with seed views[v].seed, n_v samples and chunk c
+ *     (gs_multi_render_views with that one view; gs_multi_accum_* on that camera) -- for any split
+ *     into passes, any subset history, any other cameras in the batch, any rank count, any tile
+ *     size, and across a checkpoint.  Why: sample s of pixel p of a view draws from
+ *     stream_seed(seed, p, s) whichever launch runs it, and the pixel's sum is ((0 + C_0) + C_1)
+ *     + ... over chunk sums of c samples in sample order; a pass continues that sum at chunk n_v / c.
+ *  2. Counters.  The cumulative counters are the exact sums of those V renders' counters, `pixels`
+ *     counted once per view: no sample of an unselected view is ever traced, and a view with
+ *     n_v = 0 contributes nothing and resolves to 0.
+ *  3. Outputs.  A pass writes all V frames ([V][H][W][3]); an unselected view is resolved again
+ *     from its stored sums as sum / (double)n_v, so a fresh output buffer may be handed in at any
+ *     pass.
+ *  4. Per-view change.  delta[v] is the mean over the view's W H 3 values of |colour after -
+ *     colour before| in f64 (before = 0 at n_v = 0) of the last pass that selected v; an unselected
+ *     view keeps its value.  Deterministic run to run: each tile slot of a rank gives one partial
+ *     (each thread adds its pixels' terms in pixel order, the block folds them in a fixed tree),
+ *     and the host adds a view's partials rank after rank, each rank's in slot order -- no float
+ *     atomics.  Its last bits may depend on the rank count and the tile size; nothing else of a
+ *     pass does.
+ *
+ * Tiles never straddle a view: the tile height must divide H.  gs_views_tile_h(H, tile_h) is the
+ * largest divisor of H that is <= tile_h (225, 64 -> 45; 1080, 64 -> 60; 24, 16 -> 12; 64, 64 -> 64;
+ * 719, 64 -> 1: a prime H gives W x 1 tiles, which is allowed, if not fast); 0 for bad arguments.
+ * By the views contract the tile size moves no bit of a frame.
+ *
+ * The tile-level primitive, stateless, the sibling of gs_render_tiles_pass_async and
+ * gs_render_tiles_views_async: renders samples [b, b + samples) of the selected views' pixels
+ * among this rank's tiles of the tall frame, b being the selected views' common view_samples
+ * value (the launch's one sample base), adds them to d_sums (device, capacity * 3 f64 in packed
+ * order, owned by the caller, zeroed before the first pass), and resolves EVERY packed pixel into
+ * out->rgb / out->rgb8.  view_samples: host, V counts, the samples each view's sums hold before
+ * the pass.  selected: host, V bytes (non-zero: render the view), NULL = every view.  The
+ * megakernel runs on a tile order of its own in which the unselected views' tiles are empty
+ * slots (their pixels retire without a camera ray) and every selected tile keeps the slot it has
+ * in `part`, so the packed sums never move; part->d_tile_order may therefore be any order of the
+ * tall frame's tiles.  d_delta_partials (device, nullable): capacity / (tile_w tile_h) doubles,
+ * one per tile slot, the sum of |colour after - colour before| over the slot's real pixels and
+ * channels (0 for a slot that is empty or of an unselected view).  d_counters is accumulated
+ * into; the kernel counts `pixels` for the selected views in every pass, so a caller summing
+ * passes takes `pixels` from a view's first pass alone.
+ * GS_ERR_ARG, before any device work and with a gs_last_error message: the views call's rules
+ * (NULL pointers, 0 views, views that differ in size, max_depth 0, samples not whole chunks or more
+ * than 64 chunks, the 32-bit limits, the partial budget), a NULL d_sums or view_samples, a
+ * view_samples value that is not whole chunks, an empty selection, selected views that hold
+ * different counts, a count that would pass 2^32, a tile_h that does not divide H.  A scene that
+ * needs the catch-all kernel: GS_ERR_UNSUPPORTED. */
+int32_t gs_views_tile_h(int32_t height, int32_t tile_h);
+gs_status gs_render_tiles_views_pass_async(const gs_device_scene* scene, const gs_view* views, uint32_t n_views,
+                                           const uint32_t* view_samples, const uint8_t* selected, uint32_t samples,
+                                           uint32_t chunk, const gs_partition* part, double* d_sums,
+                                           const gs_render_outputs* out, double* d_delta_partials,
+                                           gs_counters* d_counters, void* stream);
+
+/* The frame context's views accumulation.  gs_multi_views_accum_begin fixes the views and the
+ * chunk, cuts the tall frame round-robin into tile_w x gs_views_tile_h(H, tile_h) tiles and
+ * allocates zeroed sums on every rank.  Each gs_multi_views_accum_pass renders the next `samples`
+ * samples of the selected views (selected: V bytes, NULL = all; they must all hold the same count,
+ * else GS_ERR_ARG -- a caller with uneven counts runs one pass per count) and delivers all V
+ * frames like gs_multi_render_views: out->rgb / out->rgb8 are [V][H][W][3] (ppm_text must be NULL),
+ * NULL `out` leaves them on the first device (gs_multi_frame); `stats` describes this pass alone.
+ * While it is open gs_multi_render, gs_multi_render_views, gs_multi_accum_begin and
+ * gs_multi_adapt_begin return GS_ERR_ARG, and gs_multi_views_accum_begin does while an
+ * accumulation or adaptation is open; calls without an open views accumulation return GS_ERR_ARG.
+ * gs_multi_views_accum_end closes it and frees the sums (gs_multi_destroy does too). */
+typedef struct gs_views_accum_info {
+    int32_t width, height;  /* of one view */
+    uint32_t n_views;
+    uint32_t chunk;         /* the coarse chunk c (resolved: never 0) */
+    uint32_t passes;        /* passes run since _begin / _upload */
+    int32_t tile_h;         /* gs_views_tile_h(height, the context's tile height) */
+    gs_counters counters;   /* cumulative; the sum of the V one-shot renders' (`pixels` once per view) */
+} gs_views_accum_info;
+gs_status gs_multi_views_accum_begin(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk);
+gs_status gs_multi_views_accum_pass(gs_multi* m, uint32_t samples, const uint8_t* selected,
+                                    const gs_multi_outputs* out, gs_stats* stats);
+/* view_samples_out (V u32) and delta_out (V f64) may be NULL. */
+gs_status gs_multi_views_accum_info(const gs_multi* m, gs_views_accum_info* info, uint32_t* view_samples_out,
+                                    double* delta_out);
+/* Checkpoints: the sums in image order, [V][H][W][3] f64 (host), so sums saved on N ranks resume on
+ * M.  gs_multi_views_accum_upload opens a views accumulation like _begin and fills it: view v's
+ * sums hold view_samples[v] samples (whole chunks), `counters` are the cumulative counters saved
+ * with them.  The deltas start at 0.  Not hot: the tile permutation runs on the host. */
+gs_status gs_multi_views_accum_download(gs_multi* m, double* sums);
+gs_status gs_multi_views_accum_upload(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk,
+                                      const uint32_t* view_samples, const double* sums, const gs_counters* counters);
+gs_status gs_multi_views_accum_end(gs_multi* m);
 
 /* Path of the RCCL library gs_render_multi uses (loaded on this call), or NULL. */
 const char* gs_rccl_library(void);
