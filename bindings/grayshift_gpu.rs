@@ -155,6 +155,14 @@ pub struct gs_views_accum_info {
     pub counters: gs_counters,
 }
 
+/// An open views adaptation of the frame context (adaptive views; additive, ABI 11).
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_views_adapt_info {
+    pub width: i32, pub height: i32, pub n_views: u32, pub tile_h: i32, pub batch: u32, pub rounds: u32,
+    pub max_rounds: u32, pub finished: u32, pub active_pixels: u64, pub samples_total: u64, pub samples_max: u64,
+    pub counters: gs_counters,
+}
+
 /// An open adaptation of the frame context (progressive adaptive passes; additive, ABI 11).
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct gs_adapt_info {
@@ -312,6 +320,25 @@ extern "C" {
                                        view_samples: *const u32, sums: *const f64,
                                        counters: *const gs_counters) -> gs_status;
     pub fn gs_multi_views_accum_end(m: *mut gs_multi) -> gs_status;
+    // Adaptive views (additive, ABI 11): a batch of views under one gs_sample_settings, in batch
+    // rounds on the tall frame; view v's frames and maps are the bits of its own adaptive render.
+    pub fn gs_render_tiles_views_rounds_async(scene: *const gs_device_scene, views: *const gs_view, n_views: u32,
+                                              ss: *const gs_sample_settings, part: *const gs_partition,
+                                              first_round: u32, rounds: u32, d_state: *mut c_void, state_bytes: i64,
+                                              out: *const gs_round_outputs, d_counters: *mut gs_counters,
+                                              stream: *mut c_void) -> gs_status;
+    pub fn gs_multi_views_adapt_begin(m: *mut gs_multi, views: *const gs_view, n_views: u32,
+                                      ss: *const gs_sample_settings) -> gs_status;
+    pub fn gs_multi_views_adapt_pass(m: *mut gs_multi, rounds: u32, out: *const gs_multi_outputs,
+                                     stats: *mut gs_stats) -> gs_status;
+    pub fn gs_multi_views_adapt_info(m: *mut gs_multi, info: *mut gs_views_adapt_info,
+                                     view_active_out: *mut u64) -> gs_status;
+    pub fn gs_multi_views_adapt_maps(m: *mut gs_multi, samples: *mut u32, rel_error: *mut f32) -> gs_status;
+    pub fn gs_multi_views_adapt_download(m: *mut gs_multi, sums: *mut f64, state: *mut u32) -> gs_status;
+    pub fn gs_multi_views_adapt_upload(m: *mut gs_multi, views: *const gs_view, n_views: u32,
+                                       ss: *const gs_sample_settings, rounds_done: u32, sums: *const f64,
+                                       state: *const u32, counters: *const gs_counters) -> gs_status;
+    pub fn gs_multi_views_adapt_end(m: *mut gs_multi) -> gs_status;
 }
 
 pub fn last_error() -> String {

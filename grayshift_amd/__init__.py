@@ -15,6 +15,7 @@ _EXPORTS = {
     "set_tuning": "renderer", "write_ppm": "renderer", "render_ppm": "renderer", "ppm_encode_async": "renderer",
     "render_multi": "renderer", "MultiRenderer": "renderer", "ProgressiveRenderer": "renderer",
     "AdaptiveRenderer": "renderer", "render_views": "renderer", "ViewsProgressiveRenderer": "renderer",
+    "ViewsAdaptiveRenderer": "renderer", "render_views_adaptive": "renderer",
     "SceneBuilder": "scene", "camera_spec": "scene", "fixed_spp": "scene", "sample_settings": "scene",
 }
 _SUBMODULES = {"scenes", "partition", "assets", "_native", "scene", "codeobj", "checkpoint"}

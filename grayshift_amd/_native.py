@@ -196,6 +196,18 @@ class gs_views_accum_info(C.Structure):
         return d
 
 
+class gs_views_adapt_info(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_views", C.c_uint32), ("tile_h", C.c_int32),
+                ("batch", C.c_uint32), ("rounds", C.c_uint32), ("max_rounds", C.c_uint32), ("finished", C.c_uint32),
+                ("active_pixels", C.c_uint64), ("samples_total", C.c_uint64), ("samples_max", C.c_uint64),
+                ("counters", gs_counters)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "counters"}
+        d["counters"] = self.counters.as_dict()
+        return d
+
+
 # Every symbol include/*.h declares, with its ctypes signature.
 _P = C.c_void_p
 SIGNATURES = {
@@ -295,6 +307,18 @@ SIGNATURES = {
     "gs_multi_views_accum_upload": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, C.c_uint32, _P, _P,
                                                 C.POINTER(gs_counters)]),
     "gs_multi_views_accum_end": (C.c_int32, [_P]),
+    "gs_render_tiles_views_rounds_async": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32,
+                                                       C.POINTER(gs_sample_settings), C.POINTER(gs_partition),
+                                                       C.c_uint32, C.c_uint32, _P, C.c_int64,
+                                                       C.POINTER(gs_round_outputs), _P, _P]),
+    "gs_multi_views_adapt_begin": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, C.POINTER(gs_sample_settings)]),
+    "gs_multi_views_adapt_pass": (C.c_int32, [_P, C.c_uint32, C.POINTER(gs_multi_outputs), C.POINTER(gs_stats)]),
+    "gs_multi_views_adapt_info": (C.c_int32, [_P, C.POINTER(gs_views_adapt_info), _P]),
+    "gs_multi_views_adapt_maps": (C.c_int32, [_P, _P, _P]),
+    "gs_multi_views_adapt_download": (C.c_int32, [_P, _P, _P]),
+    "gs_multi_views_adapt_upload": (C.c_int32, [_P, C.POINTER(gs_view), C.c_uint32, C.POINTER(gs_sample_settings),
+                                                C.c_uint32, _P, _P, C.POINTER(gs_counters)]),
+    "gs_multi_views_adapt_end": (C.c_int32, [_P]),
     # grayshift_host.h
     "gs_host_scene_from_spec": (C.c_int32, [C.POINTER(gs_scene_spec), C.POINTER(_P)]),
     "gs_host_scene_destroy": (C.c_int32, [_P]),

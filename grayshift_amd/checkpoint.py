@@ -26,8 +26,10 @@ An adaptive frame in progress (``AdaptiveRenderer``) is format ``ADAPTIVE_FORMAT
 
 ``read_checkpoint`` rejects it, and ``read_adaptive_checkpoint`` rejects format 1: neither
 renderer can resume the other's file.  A batch of views in progress (``ViewsProgressiveRenderer``)
-is format ``VIEWS_FORMAT`` (3), described with its functions at the end of this file; its reader
-rejects formats 1 and 2, and their readers reject it.
+is format ``VIEWS_FORMAT`` (3), described with its functions below; its reader rejects formats 1
+and 2, and their readers reject it.  A batch of views under adaptive settings in progress
+(``ViewsAdaptiveRenderer``) is format ``VIEWS_ADAPTIVE_FORMAT`` (4), at the end of this file;
+its reader rejects formats 1 to 3, and their readers reject it.
 """
 import numpy as np
 
@@ -290,3 +292,112 @@ def check_views_compatible(meta, width, height, chunk, seeds, cameras, samples=N
             raise CheckpointError("checkpoint camera of view %d differs from the batch's" % v)
     if samples is not None and [int(n) for n in samples] != list(meta["samples"]):
         raise CheckpointError("checkpoint samples %r differ from %r" % (list(meta["samples"]), [int(n) for n in samples]))
+
+
+# ------------------------------------------------------------------ adaptive views (format 4)
+# A batch of views under adaptive settings in progress (``ViewsAdaptiveRenderer``):
+#
+# * ``sums``    -- [V, H, W, 5] f64: Σr, Σg, Σb, Σlum, Σlum² per pixel of every view, image order;
+# * ``state``   -- [V, H, W] u32: batches taken, the top bit set once the pixel has stopped;
+# * ``rounds``  -- the rounds run (one count for the batch: every active pixel takes every round);
+# * ``seeds``   -- [V] u64; ``cameras`` -- [V, sizeof(gs_camera)] u8;
+# * ``width``, ``height`` -- the size of one view;
+# * ``confidence``, ``tolerance``, ``batch_size``, ``max_samples`` -- the batch's one SampleSettings;
+# * ``counters`` -- the cumulative work counters, in ``COUNTER_NAMES`` order.
+#
+# Its reader rejects formats 1 to 3, and their readers reject it.
+VIEWS_ADAPTIVE_FORMAT = 4
+VIEWS_ADAPTIVE_REQUIRED = ("rounds", "seeds", "cameras", "width", "height", "counters") + SETTINGS
+
+
+def _check_views_adaptive(sums, state, meta):
+    v, h, w = len(meta["seeds"]), meta["height"], meta["width"]
+    if v == 0:
+        raise CheckpointError("a views checkpoint of 0 views")
+    if len(meta["cameras"]) != v:
+        raise CheckpointError("%d seeds, %d cameras" % (v, len(meta["cameras"])))
+    if len({len(c) for c in meta["cameras"]}) != 1:
+        raise CheckpointError("cameras of different byte lengths")
+    if sums.shape != (v, h, w, 5) or state.shape != (v, h, w):
+        raise CheckpointError("sums of shape %r, state of shape %r for %d adaptive views of %d x %d" %
+                              (sums.shape, state.shape, v, w, h))
+    # (the per-pixel rules are format 2's, on the tall frame)
+    _check_adaptive(sums.reshape(v * h, w, 5), state.reshape(v * h, w), dict(meta, height=v * h))
+
+
+def write_views_adaptive_checkpoint(path, sums, state, meta):
+    """Write `sums` ([V, H, W, 5] f64), `state` ([V, H, W] u32) and `meta` to `path` (a file name,
+    used as given, or a file object).  meta: rounds, width, height, batch_size, max_samples (ints),
+    confidence, tolerance (floats), seeds (V ints), cameras (V byte strings), counters (a dict by
+    COUNTER_NAMES)."""
+    for k in VIEWS_ADAPTIVE_REQUIRED:
+        if k not in meta:
+            raise CheckpointError("checkpoint meta lacks %r" % k)
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    state = np.ascontiguousarray(state, dtype=np.uint32)
+    m = {k: int(meta[k]) for k in ("rounds", "width", "height", "batch_size", "max_samples")}
+    m["seeds"] = [int(s) for s in meta["seeds"]]
+    m["cameras"] = [bytes(c) for c in meta["cameras"]]
+    _check_views_adaptive(sums, state, m)
+    v = len(m["seeds"])
+    counters = np.array([int(meta["counters"][n]) for n in COUNTER_NAMES], dtype=np.uint64)
+    fields = dict(format=np.int64(VIEWS_ADAPTIVE_FORMAT), sums=sums, state=state, rounds=np.uint32(m["rounds"]),
+                  seeds=np.array(m["seeds"], dtype=np.uint64),
+                  cameras=np.frombuffer(b"".join(m["cameras"]), dtype=np.uint8).reshape(v, -1),
+                  width=np.int32(m["width"]), height=np.int32(m["height"]),
+                  confidence=np.float64(meta["confidence"]), tolerance=np.float64(meta["tolerance"]),
+                  batch_size=np.uint32(m["batch_size"]), max_samples=np.uint32(m["max_samples"]), counters=counters)
+    if hasattr(path, "write"):
+        np.savez(path, **fields)
+    else:
+        with open(path, "wb") as f:  # (the name as given: numpy would add ".npz" to it)
+            np.savez(f, **fields)
+
+
+def read_views_adaptive_checkpoint(path):
+    """-> (sums [V, H, W, 5] f64, state [V, H, W] u32, meta) as write_views_adaptive_checkpoint took
+    them."""
+    with np.load(path, allow_pickle=False) as z:
+        if "format" not in z.files or int(z["format"]) != VIEWS_ADAPTIVE_FORMAT:
+            raise CheckpointError("not a grayshift adaptive views checkpoint (format %d)" % VIEWS_ADAPTIVE_FORMAT)
+        for k in VIEWS_ADAPTIVE_REQUIRED + ("sums", "state"):
+            if k not in z.files:
+                raise CheckpointError("checkpoint lacks %r" % k)
+        sums = np.ascontiguousarray(z["sums"], dtype=np.float64)
+        state = np.ascontiguousarray(z["state"], dtype=np.uint32)
+        cams = np.ascontiguousarray(z["cameras"], dtype=np.uint8)
+        if cams.ndim != 2:
+            raise CheckpointError("cameras of shape %r" % (cams.shape,))
+        meta = {"rounds": int(z["rounds"]), "seeds": [int(s) for s in z["seeds"]],
+                "cameras": [c.tobytes() for c in cams], "width": int(z["width"]), "height": int(z["height"]),
+                "confidence": float(z["confidence"]), "tolerance": float(z["tolerance"]),
+                "batch_size": int(z["batch_size"]), "max_samples": int(z["max_samples"]),
+                "counters": {n: int(v) for n, v in zip(COUNTER_NAMES, z["counters"])}}
+    _check_views_adaptive(sums, state, meta)
+    return sums, state, meta
+
+
+def check_views_adaptive_compatible(meta, width, height, settings, seeds, cameras):
+    """Raise CheckpointError unless the checkpoint's view count, view size, seeds, camera bytes and
+    the four SampleSettings fields are the ones given (the batch a caller resumes on).  settings: as
+    for check_adaptive_compatible.  The world itself is not compared."""
+    def get(k):
+        return settings[k] if isinstance(settings, dict) else getattr(settings, k)
+    seeds, cameras = [int(s) for s in seeds], [bytes(c) for c in cameras]
+    if len(meta["seeds"]) != len(cameras) or len(seeds) != len(cameras):
+        raise CheckpointError("checkpoint of %d views, a batch of %d cameras and %d seeds" %
+                              (len(meta["seeds"]), len(cameras), len(seeds)))
+    for name, have, want in (("width", meta["width"], int(width)), ("height", meta["height"], int(height)),
+                             ("batch_size", meta["batch_size"], int(get("batch_size"))),
+                             ("max_samples", meta["max_samples"], int(get("max_samples")))):
+        if have != want:
+            raise CheckpointError("checkpoint %s %d differs from the batch's %d" % (name, have, want))
+    for name in ("confidence", "tolerance"):
+        if np.float64(meta[name]).tobytes() != np.float64(get(name)).tobytes():
+            raise CheckpointError("checkpoint %s %r differs from the batch's %r" % (name, meta[name], get(name)))
+    for v, (have, want) in enumerate(zip(meta["seeds"], seeds)):
+        if have != want:
+            raise CheckpointError("checkpoint seed %d of view %d differs from the batch's %d" % (have, v, want))
+    for v, (have, want) in enumerate(zip(meta["cameras"], cameras)):
+        if have != want:
+            raise CheckpointError("checkpoint camera of view %d differs from the batch's" % v)

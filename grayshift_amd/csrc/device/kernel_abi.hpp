@@ -58,9 +58,11 @@
                              // chunk != 0, max_depth > 0) -- the fixed kernel's sample loop, its items
                              // taken from the round's active list and each sample's colour written for
                              // the combine; no stop test, Σlum or batch end in the kernel (round 6)
-#define GS_FEAT_VIEWS 2048   // with GS_FEAT_FIXED: a batch of cameras as one tall frame (KParams.views; the views
-                             // calls, gs_render_tiles_views_async): the camera-ray step takes its camera, seed
-                             // and max_depth from the record of the view the pixel lies in
+#define GS_FEAT_VIEWS 2048   // a batch of cameras as one tall frame (KParams.views; the views calls,
+                             // gs_render_tiles_views_async): the camera-ray step takes its camera, seed
+                             // and max_depth from the record of the view the pixel lies in.  With
+                             // GS_FEAT_FIXED (fixed spp), with GS_FEAT_FIXED | GS_FEAT_RSPLIT or alone (a
+                             // views adaptation's split rounds: views_round_kernel_for)
 #ifndef GS_NODE_STEPS
 #define GS_NODE_STEPS 8  // node steps per unrolled node pass (the render kernel, below)
 #endif

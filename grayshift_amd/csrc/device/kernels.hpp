@@ -11,6 +11,12 @@ bool has_rsplit(int feat);
 // A views launch may take the (feat | GS_FEAT_FIXED | GS_FEAT_VIEWS) instantiation (for such a
 // feature set kernel_for returns null when there is none: a views launch has no fallback).
 bool has_views(int feat);
+// The split batch round of a views adaptation: the (feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT |
+// GS_FEAT_VIEWS) instantiation where has_rsplit(feat), else (feat | GS_FEAT_VIEWS), the loop's
+// kernel with per-sample items; null for any other word (no fallback).  has_views_rounds: the
+// feature set has one of the two.
+void (*views_round_kernel_for(int feat))(KArgs);
+bool has_views_rounds(int feat);
 
 // Each enqueues one kernel on `st` and returns that launch's error (hipGetLastError()).
 hipError_t launch_params_kernel(hipStream_t st, const KParams& kp, KParams* dst);  // (zeroes the queue)

@@ -1188,8 +1188,11 @@ __global__ __launch_bounds__(GS_BLOCK, GS_MIN_WAVES) void gs_render_kernel(KArgs
     // ... or a batch round's split items in that form (GS_FEAT_RSPLIT: per-sample colours)
     constexpr bool kRsplit = kFixed && (FEAT & GS_FEAT_RSPLIT) != 0;
     constexpr bool kGeneral = (FEAT & GS_FEAT_GENERAL) != 0;
-    // ... or of a batch of cameras stacked into one tall frame (GS_FEAT_VIEWS: KParams.views)
-    constexpr bool kViews = kFixed && (FEAT & GS_FEAT_VIEWS) != 0;
+    // A batch of cameras stacked into one tall frame (GS_FEAT_VIEWS: KParams.views) -- of the fixed
+    // kernel, of a split batch round in its form (with GS_FEAT_RSPLIT) or of one in the loop's
+    // (without GS_FEAT_FIXED: views_round_kernel_for).  Only the camera-ray step reads it: the
+    // claim block's bounds test and L_PIX are the tall frame's.
+    constexpr bool kViews = (FEAT & GS_FEAT_VIEWS) != 0;
     // (t_in_lds kernels: the throughput's three fields first, at fixed offsets)
 #define LD(k) s_d[((k) + (t_in_lds(FEAT) ? 3 : 0)) * GS_BLOCK + tid]
 #define LI(k) s_i[(k) * GS_BLOCK + tid]
@@ -3015,6 +3018,60 @@ bool has_views(int feat) {
     return (feat & (GS_FEAT_GENERAL | GS_FEAT_VISITS)) == 0 && kernel_for(feat | GS_FEAT_FIXED | GS_FEAT_VIEWS) != nullptr;
 #endif
 }
+// The split batch round of a views adaptation (gs_render_tiles_views_rounds_async), a table of its
+// own: one instantiation per product feature set that has a views form.  GS_VR: the sets of
+// kernel_for's GS_KR lines (and the empty set), in the fixed kernel's sample loop over the round's
+// items (F | FIXED | RSPLIT | VIEWS).  GS_VL: the six media / nested-BVH sets of its GS_K lines, in
+// the loop's kernel with per-sample split items (F | VIEWS), as a plain round pass runs them.
+// Null for every other word: a views launch has no fallback.
+void (*views_round_kernel_for(int feat))(KArgs) {
+#ifdef GS_ONLY_FEAT
+    (void)feat;
+    return nullptr;
+#else
+#define GS_VR(F) \
+    case (F) | GS_FEAT_FIXED | GS_FEAT_RSPLIT | GS_FEAT_VIEWS: return gs_render_kernel<(F) | GS_FEAT_FIXED | GS_FEAT_RSPLIT | GS_FEAT_VIEWS>;
+#define GS_VL(F) \
+    case (F) | GS_FEAT_VIEWS: return gs_render_kernel<(F) | GS_FEAT_VIEWS>;
+    switch (feat) {
+        GS_VL(GS_FEAT_MEDIA)
+        GS_VL(GS_FEAT_NESTED)
+        GS_VL(GS_FEAT_MEDIA | GS_FEAT_NESTED)
+        GS_VR(GS_FEAT_LEAFRUN)
+        GS_VL(GS_FEAT_LEAFRUN | GS_FEAT_MEDIA)
+        GS_VL(GS_FEAT_LEAFRUN | GS_FEAT_NESTED)
+        GS_VL(GS_FEAT_LEAFRUN | GS_FEAT_MEDIA | GS_FEAT_NESTED)
+        GS_VR(GS_FEAT_LDSTREE)
+        GS_VR(GS_FEAT_LDSTREE | GS_FEAT_LEAFRUN)
+        GS_VR(GS_FEAT_MIXED)
+        GS_VR(GS_FEAT_MIXED | GS_FEAT_LEAFRUN)
+        GS_VR(GS_FEAT_MIXED | GS_FEAT_LDSTREE)
+        GS_VR(GS_FEAT_MIXED | GS_FEAT_LDSTREE | GS_FEAT_LEAFRUN)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN | GS_FEAT_LDSTREE)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN | GS_FEAT_MIXED)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN | GS_FEAT_MIXED | GS_FEAT_LDSTREE)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN | GS_FEAT_MIXED | GS_FEAT_PLAIN)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_LEAFRUN | GS_FEAT_MIXED | GS_FEAT_PLAIN | GS_FEAT_LDSTREE)
+        GS_VR(GS_FEAT_SPHLEAF)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_LDSTREE)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_MIXED)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_MIXED | GS_FEAT_LDSTREE)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_MIXED | GS_FEAT_PLAIN)
+        GS_VR(GS_FEAT_SPHLEAF | GS_FEAT_MIXED | GS_FEAT_PLAIN | GS_FEAT_LDSTREE)
+        GS_VR(0)
+        default: return nullptr;
+    }
+#undef GS_VR
+#undef GS_VL
+#endif
+}
+// A views adaptation's rounds have an instantiation for the scene's feature set, in either form.
+bool has_views_rounds(int feat) {
+    return views_round_kernel_for(feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT | GS_FEAT_VIEWS) != nullptr ||
+           views_round_kernel_for(feat | GS_FEAT_VIEWS) != nullptr;
+}
+
 // The views of a views launch, at most GS_VIEW_BATCH per call: by value, like gs_params_kernel's
 // block, so the caller's array is read before the call returns.
 hipError_t launch_views_kernel(hipStream_t st, const ViewBatch& vb, gs_view* dst) {

@@ -270,7 +270,7 @@ int64_t gs_host_struct_size(const char* name) {
     GS_SZ(gs_background) GS_SZ(gs_flat_scene) GS_SZ(gs_camera) GS_SZ(gs_partition)
     GS_SZ(gs_render_outputs) GS_SZ(gs_launch) GS_SZ(gs_multi_outputs) GS_SZ(gs_stats) GS_SZ(gs_scene_info)
     GS_SZ(gs_accum_info) GS_SZ(gs_adapt_info) GS_SZ(gs_round_outputs) GS_SZ(gs_view)
-    GS_SZ(gs_views_accum_info)
+    GS_SZ(gs_views_accum_info) GS_SZ(gs_views_adapt_info)
 #undef GS_SZ
     return -1;
 }

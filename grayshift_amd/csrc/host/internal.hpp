@@ -60,6 +60,14 @@ gs_status gs_render_tiles_rounds_timed_async(const gs_device_scene* ds, const gs
                                              uint32_t first_round, uint32_t rounds, void* d_state, int64_t state_bytes,
                                              const gs_round_outputs* out, gs_counters* d_counters, void* stream,
                                              hipEvent_t k_begin, hipEvent_t k_end, bool direct, bool zero_counters);
+// gs_render_tiles_views_rounds_async with the same extras (rounds == 0, this form only: resolve
+// the state as it stands; direct: out->rgb / rgb8 are the [V][H][W][3] frames).
+gs_status gs_render_tiles_views_rounds_timed_async(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                                   const gs_sample_settings* ss, const gs_partition* part,
+                                                   uint32_t first_round, uint32_t rounds, void* d_state,
+                                                   int64_t state_bytes, const gs_round_outputs* out,
+                                                   gs_counters* d_counters, void* stream, hipEvent_t k_begin,
+                                                   hipEvent_t k_end, bool direct, bool zero_counters);
 // The round-state blob of `cap` packed pixels and R rounds, byte offsets (256-B aligned but the
 // first three): the item-size hint, the summary (4 u64), round_counts[R + 2], the two active
 // lists (cap u32 each), pstate (cap * 5 f64), the batches words (cap u32).  Private to the

@@ -497,6 +497,55 @@ gs_status gs_render_tiles_rounds_timed_async(const gs_device_scene* ds, const gs
                   nullptr, &ra);
 }
 
+// ---------------------------------------------------------------- adaptive views
+// A views adaptation's pass: the views' rules and the rounds' rules on the tall frame, all on the
+// arguments alone, then the round pass with the views' records (launch: RoundArgs and ViewsArgs).
+static gs_status check_views_rounds(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                    const gs_sample_settings* ss, const gs_partition* part, uint32_t first_round,
+                                    uint32_t rounds, const void* d_state, int64_t state_bytes,
+                                    const gs_round_outputs* out, bool zero_rounds, gs_camera* tall) {
+    gs_status e = gs_views_check(ds, views, n_views, 1, 1, tall);  // (one sample, one chunk: the views' own rules)
+    if (e == GS_OK) e = check_rounds(ds, tall, ss, part, first_round, rounds, d_state, state_bytes, out, zero_rounds);
+    if (e != GS_OK) return e;
+    if (views[0].cam.image_height % part->tile_h != 0)
+        return fail(GS_ERR_ARG, "tile_h does not divide the views' height (gs_views_tile_h): a tile would straddle two views");
+    return GS_OK;
+}
+
+gs_status gs_render_tiles_views_rounds_timed_async(const gs_device_scene* ds, const gs_view* views, uint32_t n_views,
+                                                   const gs_sample_settings* ss, const gs_partition* part,
+                                                   uint32_t first_round, uint32_t rounds, void* d_state,
+                                                   int64_t state_bytes, const gs_round_outputs* out,
+                                                   gs_counters* d_counters, void* stream, hipEvent_t k_begin,
+                                                   hipEvent_t k_end, bool direct, bool zero_counters) {
+    gs_camera tall;
+    gs_status e = check_views_rounds(ds, views, n_views, ss, part, first_round, rounds, d_state, state_bytes, out, true, &tall);
+    if (e != GS_OK) return e;
+    if (!has_views_rounds(ds->feat))
+        return fail(GS_ERR_UNSUPPORTED, "the scene needs the catch-all kernel, which has no views form");
+    e = ensure_placement(const_cast<gs_device_scene*>(ds), &views[0].cam, ss, stream);  // (view 0's own frame)
+    if (e != GS_OK) return e;
+    const RoundArgs ra{first_round, rounds, ss->max_samples / ss->batch_size + 1u, (uint8_t*)d_state, out->samples,
+                       out->rel_error};
+    const ViewsArgs vw{views, n_views, 0};
+    const gs_render_outputs o{out->rgb, out->rgb8, nullptr};
+    return launch(ds, &tall, ss, 0, part, &o, d_counters, stream, k_begin, k_end, nullptr, direct, zero_counters, nullptr,
+                  &ra, &vw);
+}
+
+extern "C" gs_status gs_render_tiles_views_rounds_async(const gs_device_scene* ds, const gs_view* views,
+                                                        uint32_t n_views, const gs_sample_settings* ss,
+                                                        const gs_partition* part, uint32_t first_round,
+                                                        uint32_t rounds, void* d_state, int64_t state_bytes,
+                                                        const gs_round_outputs* out, gs_counters* d_counters,
+                                                        void* stream) {
+    gs_camera tall;
+    gs_status e = check_views_rounds(ds, views, n_views, ss, part, first_round, rounds, d_state, state_bytes, out, false, &tall);
+    if (e != GS_OK) return e;
+    return gs_render_tiles_views_rounds_timed_async(ds, views, n_views, ss, part, first_round, rounds, d_state,
+                                                    state_bytes, out, d_counters, stream, nullptr, nullptr, false, false);
+}
+
 extern "C" int64_t gs_round_state_bytes(const gs_camera* cam, const gs_partition* part, const gs_sample_settings* ss) {
     if (!cam || !part || !ss || ss->batch_size == 0 || ss->max_samples < ss->batch_size) return -1;
     const int64_t cap = gs_partition_capacity(cam, part);
@@ -903,6 +952,12 @@ struct Enqueue {
         ds->last_launch_feat.store(f);
         return kernel_for(f);
     }
+    // views_round_kernel_for(f), noted likewise when it exists
+    void (*views_round_kernel(int f) const)(KArgs) {
+        void (*kn)(KArgs) = views_round_kernel_for(f);
+        if (kn) ds->last_launch_feat.store(f);
+        return kn;
+    }
 };
 
 // Batch rounds: init (every real packed pixel active), then per round and segment: parameters,
@@ -937,17 +992,21 @@ static gs_status enqueue_rounds(const Enqueue& q, const WorkPlan& w, const Knobs
 // for an earlier pass -- always in split items (whole-batch items take the stop test in the
 // megakernel, which does not write the persistent state), the fold in the combine's place;
 // then the resolve over every packed pixel.
+// views: a views adaptation's pass -- the same rounds on the tall frame, in the views form of the
+// round's kernel (views_round_kernel_for; every view's max_depth > 0), which has no fallback.
 static gs_status enqueue_round_pass(const Enqueue& q, const WorkPlan& w, const Knobs& k, const LaunchReq& r,
-                                    const RoundArgs& ra, const KParams& kp, KParams* dP, const KArgs& a) {
+                                    const RoundArgs& ra, const KParams& kp, KParams* dP, const KArgs& a, bool views) {
     const hipStream_t st = q.st;
+    const bool rsplit = GS_USE_RSPLIT && has_rsplit(q.feat) && r.cam->max_depth > 0;
+    const int rfeat = (rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat) | (views ? GS_FEAT_VIEWS : 0);
+    void (*rkern)(KArgs) = views ? q.views_round_kernel(rfeat) : q.kernel(rfeat);
+    if (!rkern) return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's round kernel in this build");
     if (ra.first_round == 0 && ra.rounds) {
         const unsigned g_init = (unsigned)std::min<int64_t>(((int64_t)r.cap + 255) / 256, 8192);
         HIPCHK(launch_round_init_kernel(st, g_init, dP));
     }
     if (q.k_begin) HIPCHK(hipEventRecord(q.k_begin, st));
     const unsigned g_fold = (unsigned)std::min<int64_t>((w.seg_px + 255) / 256, 8192);
-    const bool rsplit = GS_USE_RSPLIT && has_rsplit(q.feat) && r.cam->max_depth > 0;
-    void (*rkern)(KArgs) = q.kernel(rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat);
     for (uint32_t rd = ra.first_round; rd < ra.first_round + ra.rounds; rd++)
         for (uint32_t sg = 0; sg < w.n_segs; sg++) {
             HIPCHK(launch_round_params_kernel(st, dP, rd, sg, w.seg_px, k.sample_chunk, 0));
@@ -1019,16 +1078,17 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     const uint64_t lanes = (uint64_t)std::max(1, device_cus(dev)) * GS_BLOCK;
     const bool long_samples = ds->long_samples.load(std::memory_order_relaxed);
     // (a views launch: a pass's plan on the tall frame -- always chunked, the chunk as given)
-    WorkPlan w = pass || vw ? plan_pass(*cam, ss->batch_size, *part, req.cap, pass ? pass->chunk : vw->chunk, ds->feat, k,
-                                        lanes, long_samples)
-                      : plan_work(*cam, *ss, *part, req.cap, ds->feat, k, lanes, long_samples, !visit_out && !va);
+    WorkPlan w;
     if (ra) {  // always batch rounds, whatever gs_set_adaptive_mode and the sample chunk say (plan_work's layout)
-        w = WorkPlan{};
         w.n_rounds = ra->R;
         w.seg_px = (uint32_t)round_seg_px(req.cap, *ss, k);
         if (w.seg_px < 1) return fail(GS_ERR_ARG, "one pixel's batch exceeds the partial budget");
         w.n_segs = (uint32_t)(((uint64_t)req.cap + w.seg_px - 1) / w.seg_px);
         w.fine_px = req.cap;
+    } else if (pass || vw) {
+        w = plan_pass(*cam, ss->batch_size, *part, req.cap, pass ? pass->chunk : vw->chunk, ds->feat, k, lanes, long_samples);
+    } else {
+        w = plan_work(*cam, *ss, *part, req.cap, ds->feat, k, lanes, long_samples, !visit_out && !va);
     }
     // (under the scene's mutex from here: the placement pilot's end rewrites the records,
     // the root and the mirror prefixes under it, pilot_end)
@@ -1079,7 +1139,8 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
         kp.map_error = ra->map_error;
     }
     if (vw) {  // the views' records into the slot's array, behind the slot's previous launch on the stream
-        if (!has_views(lc.feat)) return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's kernel");
+        if (!(ra ? has_views_rounds(lc.feat) : has_views(lc.feat)))
+            return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's kernel");
         e = grow_buffer(sl, sl.views, sl.views_bytes, (size_t)vw->n * sizeof(gs_view), "views");
         if (e != GS_OK) return e;
         for (uint32_t first = 0; first < vw->n; first += GS_VIEW_BATCH) {
@@ -1117,7 +1178,7 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     HIPCHK(launch_params_kernel(st, kp, sl.params));  // (zeroes the queue)
     if (vp_pos) HIPCHK(launch_views_order_kernel(st, sl.params, sl.vorder, vp_pos, (uint32_t)vw->views[0].cam.image_height));
     const Enqueue q{st, (unsigned)blocks, lc.lds, lc.feat, k_begin, k_end, ds};
-    e = ra ? enqueue_round_pass(q, w, k, req, *ra, kp, sl.params, a)
+    e = ra ? enqueue_round_pass(q, w, k, req, *ra, kp, sl.params, a, vw != nullptr)
         : w.n_rounds ? enqueue_rounds(q, w, k, req, kp, sl.params, a)
                      : enqueue_frame(q, w, req, sl.params, a, pass != nullptr, vw != nullptr);
     if (e != GS_OK) return e;

@@ -163,6 +163,17 @@ struct DeviceGuard {
     ~DeviceGuard() { (void)hipSetDevice(saved); }
 };
 
+// The settings rules of an adaptation, on the arguments alone.
+gs_status adapt_settings_check(const gs_sample_settings* ss) {
+    if (ss->batch_size == 0) return fail(GS_ERR_ARG, "batch_size 0 never terminates (camera.rs:137)");
+    if (ss->max_samples < ss->batch_size)
+        return fail(GS_ERR_ARG, "the settings run one batch (max_samples < batch_size): a fixed-spp frame has its "
+                                "passes in gs_multi_accum_begin");
+    if ((uint64_t)ss->max_samples / ss->batch_size + 1u > 65536u)
+        return fail(GS_ERR_ARG, "more than 65536 batches (max_samples / batch_size + 1): no round form");
+    return GS_OK;
+}
+
 int g_collective_always = 0;  // gs_debug_set_multi_collective
 int g_same_device = 0;        // gs_debug_set_multi_same_device
 
@@ -224,6 +235,11 @@ struct gs_multi {
     std::vector<uint32_t> va_samples;
     std::vector<double> va_delta;
     gs_counters va_counters{};
+    // The open views adaptation (gs_multi_views_adapt_begin .. _end): an adaptation (ad_open and
+    // every ad_* field above) whose camera is the tall frame's, cut round-robin into tw x
+    // gs_views_tile_h tiles like a views accumulation (`th`, th_ctx), with the views' records.
+    bool vd_open = false;
+    std::vector<gs_view> vd_views;
 
     ~gs_multi() {
         DeviceGuard g;
@@ -299,8 +315,19 @@ struct gs_multi {
     int32_t slot_tile(int rank, int64_t slot) const;
     // Moves the sums between the ranks' packed buffers and an [H][W][3] image (to_image or back).
     gs_status permute_sums(double* image, bool to_image);
-    gs_status adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed);
+    // views: a views adaptation (cam is then the tall frame's camera; the arguments are checked by
+    // the caller, gs_views_check)
+    gs_status adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
+                          const gs_view* views = nullptr, uint32_t n_views = 0);
+    gs_status adapt_open(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, bool round_robin);
     void adapt_end();
+    // What gs_multi_adapt_* and gs_multi_views_adapt_* share, on the open adaptation's frame (the
+    // tall one for views): a pass, the maps, the state down (sums may be NULL) and, behind
+    // adapt_begin, the state up.
+    gs_status adapt_pass(uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats);
+    gs_status adapt_maps(uint32_t* samples, float* rel_error);
+    gs_status adapt_download(double* sums, uint32_t* state);
+    gs_status adapt_fill(uint32_t rounds_done, const double* sums, const uint32_t* state, const gs_counters* counters);
     // The packed pixels of rank `rank` as its launches see them (gs_partition_capacity): `cap` under
     // a plan, fewer for the later ranks of a round-robin partition -- the size the rank's round
     // state is laid out for.
@@ -360,7 +387,8 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
     if (acc_open && !pass_samples)  // (a new plan would invalidate the packed sums)
         return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
     if (ad_open && !adapt)  // (likewise: the round state is in the plan's packed order)
-        return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
+        return fail(GS_ERR_ARG, vd_open ? "a views adaptation is open: gs_multi_views_adapt_end first"
+                                        : "an adaptation is open: gs_multi_adapt_end first");
     if (va_open && !vp)  // (likewise: the views' sums are in the packed order of its own tile height)
         return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
     DeviceGuard guard;
@@ -408,9 +436,13 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         HIPOK(hipEventRecord(d.ev[0], d.stream));
         if (adapt) {
             const gs_round_outputs ro{o.rgb, o.rgb8, (uint32_t*)d.map_samples.p, (float*)d.map_error.p};
-            s = gs_render_tiles_rounds_timed_async(d.scene, cam, ss, seed, &p, ad_rounds, adapt_rounds, d.rstate.p,
-                                                   (int64_t)d.rstate.bytes, &ro, (gs_counters*)d.cnt.p, d.stream,
-                                                   d.ev[2], d.ev[3], direct, ad_fresh);
+            s = vw ? gs_render_tiles_views_rounds_timed_async(d.scene, vw->views, vw->n, ss, &p, ad_rounds, adapt_rounds,
+                                                              d.rstate.p, (int64_t)d.rstate.bytes, &ro,
+                                                              (gs_counters*)d.cnt.p, d.stream, d.ev[2], d.ev[3], direct,
+                                                              ad_fresh)
+                   : gs_render_tiles_rounds_timed_async(d.scene, cam, ss, seed, &p, ad_rounds, adapt_rounds, d.rstate.p,
+                                                        (int64_t)d.rstate.bytes, &ro, (gs_counters*)d.cnt.p, d.stream,
+                                                        d.ev[2], d.ev[3], direct, ad_fresh);
         } else if (pass_samples) {
             HIPOK(hipMemsetAsync(d.delta.p, 0, (size_t)gs_pass_delta_blocks(cap) * 8, d.stream));
             s = gs_render_tiles_pass_timed_async(d.scene, cam, pass_samples, seed, &p, (uint32_t)acc_samples, acc_chunk,
@@ -642,6 +674,7 @@ int32_t gs_multi::slot_tile(int rank, int64_t slot) const {
 
 gs_status gs_multi::accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk) {
     if (acc_open) return fail(GS_ERR_ARG, "an accumulation is already open: gs_multi_accum_end first");
+    if (vd_open) return fail(GS_ERR_ARG, "a views adaptation is open: gs_multi_views_adapt_end first");
     if (ad_open) return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
     if (va_open) return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
@@ -727,6 +760,7 @@ gs_status gs_multi::permute_sums(double* image, bool to_image) {
 gs_status gs_multi::views_accum_begin(const gs_view* views, uint32_t n_views, uint32_t chunk) {
     if (va_open) return fail(GS_ERR_ARG, "a views accumulation is already open: gs_multi_views_accum_end first");
     if (acc_open) return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
+    if (vd_open) return fail(GS_ERR_ARG, "a views adaptation is open: gs_multi_views_adapt_end first");
     if (ad_open) return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
     gs_scene_info si{};
@@ -792,21 +826,44 @@ void gs_multi::views_accum_end() {
 }
 
 // ---------------------------------------------------------------- progressive adaptation
-gs_status gs_multi::adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed) {
+gs_status gs_multi::adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
+                                const gs_view* views, uint32_t n_views) {
+    if (!views) return adapt_open(cam, ss, seed, false);
+    if (vd_open || ad_open || acc_open || va_open) return adapt_open(cam, ss, seed, true);  // (its refusal)
+    gs_scene_info si{};
+    const gs_status si_s = gs_device_scene_info(dev[0].scene, &si);
+    if (si_s != GS_OK) return si_s;
+    if (si.feat & 512) return fail(GS_ERR_UNSUPPORTED, "the scene needs the catch-all kernel, which has no views form");
+    // the batch's own tile height, so that no tile straddles two views; the cut is redone whatever
+    // camera the last frame had (the partition's cache does not know the tile height)
+    const int32_t th_was = th;
+    th = gs_views_tile_h(views[0].cam.image_height, th_was);
+    part_ready = false;
+    const gs_status s = adapt_open(cam, ss, seed, true);
+    if (s != GS_OK) {
+        th = th_was;
+        part_ready = false;
+        return s;
+    }
+    th_ctx = th_was;
+    vd_views.assign(views, views + n_views);
+    vd_open = true;
+    return GS_OK;
+}
+
+gs_status gs_multi::adapt_open(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, bool round_robin) {
+    if (vd_open) return fail(GS_ERR_ARG, "a views adaptation is open: gs_multi_views_adapt_end first");
     if (ad_open) return fail(GS_ERR_ARG, "an adaptation is already open: gs_multi_adapt_end first");
     if (acc_open) return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
     if (va_open) return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
     if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
-    if (ss->batch_size == 0) return fail(GS_ERR_ARG, "batch_size 0 never terminates (camera.rs:137)");
-    if (ss->max_samples < ss->batch_size)
-        return fail(GS_ERR_ARG, "the settings run one batch (max_samples < batch_size): a fixed-spp frame has its "
-                                "passes in gs_multi_accum_begin");
+    gs_status s = adapt_settings_check(ss);
+    if (s != GS_OK) return s;
     const uint64_t R = (uint64_t)ss->max_samples / ss->batch_size + 1u;
-    if (R > 65536u) return fail(GS_ERR_ARG, "more than 65536 batches (max_samples / batch_size + 1): no round form");
     DeviceGuard guard;
     double plan_ms = 0.0;
-    gs_status s = partition(cam, seed, &plan_ms);
+    s = partition(cam, seed, &plan_ms, round_robin);
     if (s != GS_OK) return s;
     if (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll) return fail(GS_ERR_ARG, "bad partition");
     const GsRoundLayout l = gs_round_layout((uint64_t)cap, R);
@@ -845,7 +902,124 @@ void gs_multi::adapt_end() {
         d.map_samples.release();
         d.map_error.release();
     }
+    if (vd_open) {  // (the context's own tile height again)
+        th = th_ctx;
+        part_ready = false;
+        vd_open = false;
+    }
     ad_open = false;
+}
+
+gs_status gs_multi::adapt_pass(uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats) {
+    if (rounds == 0) return fail(GS_ERR_ARG, "a pass of 0 rounds");
+    const uint32_t todo = adapt_finished() ? 0u : std::min(rounds, ad_R - ad_rounds);
+    if (!vd_open) return render(&ad_cam, &ad_ss, ad_seed, out, stats, 0, true, todo);
+    if (out && out->ppm_text) return fail(GS_ERR_ARG, "a views pass writes no PPM text");
+    const ViewsCall vw{vd_views.data(), (uint32_t)vd_views.size(), 0};
+    return render(&ad_cam, &ad_ss, 0, out, stats, 0, true, todo, &vw);
+}
+
+gs_status gs_multi::adapt_maps(uint32_t* samples, float* rel_error) {
+    DeviceGuard guard;
+    std::vector<uint8_t> packed((size_t)cap * 4);
+    for (int i = 0; i < (int)dev.size(); i++) {
+        Device& d = dev[i];
+        HIPOK(hipSetDevice(d.id));
+        HIPOK(hipStreamSynchronize(d.stream));
+        if (samples) {
+            HIPOK(hipMemcpy(packed.data(), d.map_samples.p, packed.size(), hipMemcpyDeviceToHost));
+            permute_rank(i, ad_cam, (uint8_t*)samples, packed.data(), 4, true);
+        }
+        if (rel_error) {
+            HIPOK(hipMemcpy(packed.data(), d.map_error.p, packed.size(), hipMemcpyDeviceToHost));
+            permute_rank(i, ad_cam, (uint8_t*)rel_error, packed.data(), 4, true);
+        }
+    }
+    return GS_OK;
+}
+
+gs_status gs_multi::adapt_download(double* sums, uint32_t* state) {
+    DeviceGuard guard;
+    std::vector<uint8_t> packed((size_t)cap * 40);
+    for (int i = 0; i < (int)dev.size(); i++) {
+        Device& d = dev[i];
+        const size_t rc = (size_t)rank_cap(i, ad_cam);
+        const GsRoundLayout l = gs_round_layout(rc, ad_R);
+        if (rc == 0) continue;
+        HIPOK(hipSetDevice(d.id));
+        HIPOK(hipStreamSynchronize(d.stream));
+        if (sums) {
+            HIPOK(hipMemcpy(packed.data(), (const char*)d.rstate.p + l.pstate, rc * 40, hipMemcpyDeviceToHost));
+            permute_rank(i, ad_cam, (uint8_t*)sums, packed.data(), 40, true);
+        }
+        HIPOK(hipMemcpy(packed.data(), (const char*)d.rstate.p + l.batches, rc * 4, hipMemcpyDeviceToHost));
+        permute_rank(i, ad_cam, (uint8_t*)state, packed.data(), 4, true);
+    }
+    return GS_OK;
+}
+
+// Behind adapt_begin: the state of a checkpoint into the ranks' blobs (closes the adaptation again
+// when it cannot).
+gs_status gs_multi::adapt_fill(uint32_t rounds_done, const double* sums, const uint32_t* state,
+                               const gs_counters* counters) {
+    const gs_camera* cam = &ad_cam;
+    const gs_sample_settings* ss = &ad_ss;
+    auto bail = [&](gs_status st) {
+        adapt_end();
+        return st;
+    };
+    if (rounds_done > ad_R) return bail(fail(GS_ERR_ARG, "rounds_done exceeds the settings' rounds"));
+    // every pixel's word against rounds_done: an active pixel has taken every round so far, a
+    // stopped one at least one and no more than that
+    const uint64_t npx = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
+    uint64_t active = 0, total = 0, most = 0;
+    for (uint64_t k = 0; k < npx; k++) {
+        const uint32_t nb = state[k] & ~GS_ADAPT_STOPPED;
+        const bool stopped = (state[k] & GS_ADAPT_STOPPED) != 0;
+        if (stopped ? (nb < 1 || nb > rounds_done) : (nb != rounds_done || (rounds_done == ad_R && rounds_done)))
+            return bail(fail(GS_ERR_ARG, "a pixel's state disagrees with rounds_done"));
+        active += stopped ? 0u : 1u;
+        total += (uint64_t)nb * ss->batch_size;
+        most = std::max<uint64_t>(most, (uint64_t)nb * ss->batch_size);
+    }
+    if (rounds_done == 0) {  // (nothing to fill: the first pass initialises the state)
+        ad_counters = ad_base = *counters;
+        return GS_OK;
+    }
+    DeviceGuard guard;
+    std::vector<double> psums((size_t)this->cap * 5);
+    std::vector<uint32_t> words((size_t)this->cap), list;
+    for (int i = 0; i < (int)dev.size(); i++) {
+        Device& d = dev[i];
+        const size_t cap = (size_t)rank_cap(i, *cam);  // (the rank's own: its launches lay the state out for it)
+        const GsRoundLayout l = gs_round_layout(cap, ad_R);
+        if (cap == 0) continue;
+        std::fill(psums.begin(), psums.end(), 0.0);
+        std::fill(words.begin(), words.end(), GS_ADAPT_STOPPED);  // (padding: never active)
+        permute_rank(i, *cam, (uint8_t*)const_cast<double*>(sums), (uint8_t*)psums.data(), 40, false);
+        permute_rank(i, *cam, (uint8_t*)const_cast<uint32_t*>(state), (uint8_t*)words.data(), 4, false);
+        // the round's active list, rebuilt in packed order (its order is scheduling only)
+        list.clear();
+        for (size_t k = 0; k < cap; k++) {
+            if (!(words[k] & GS_ADAPT_STOPPED)) list.push_back((uint32_t)k);
+            if (words[k] == GS_ADAPT_STOPPED) words[k] = 0u;
+        }
+        const uint32_t n_act = (uint32_t)list.size();
+        char* blob = (char*)d.rstate.p;
+        if (hipSetDevice(d.id) != hipSuccess ||
+            hipMemcpy(blob + l.pstate, psums.data(), cap * 40, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(blob + l.batches, words.data(), cap * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            (n_act && hipMemcpy(blob + l.list[rounds_done & 1u], list.data(), (size_t)n_act * 4, hipMemcpyHostToDevice) !=
+                          hipSuccess) ||
+            hipMemcpy(blob + l.counts + (size_t)rounds_done * 4, &n_act, 4, hipMemcpyHostToDevice) != hipSuccess)
+            return bail(fail(GS_ERR_HIP, "uploading the round state failed"));
+    }
+    ad_rounds = rounds_done;
+    ad_active = active;
+    ad_samples_total = total;
+    ad_samples_max = most;
+    ad_counters = ad_base = *counters;
+    return GS_OK;
 }
 
 void gs_multi::permute_rank(int rank, const gs_camera& cam, uint8_t* image, uint8_t* packed, size_t elem,
@@ -884,16 +1058,14 @@ gs_status gs_multi_adapt_begin(gs_multi* m, const gs_camera* cam, const gs_sampl
 gs_status gs_multi_adapt_pass(gs_multi* m, uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats) {
     if (!m) return fail(GS_ERR_ARG, "null context");
     std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open: gs_multi_adapt_begin first");
-    if (rounds == 0) return fail(GS_ERR_ARG, "a pass of 0 rounds");
-    const uint32_t todo = m->adapt_finished() ? 0u : std::min(rounds, m->ad_R - m->ad_rounds);
-    return m->render(&m->ad_cam, &m->ad_ss, m->ad_seed, out, stats, 0, true, todo);
+    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open: gs_multi_adapt_begin first");
+    return m->adapt_pass(rounds, out, stats);
 }
 
 gs_status gs_multi_adapt_info(const gs_multi* m, gs_adapt_info* info) {
     if (!m || !info) return fail(GS_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open");
     std::memset(info, 0, sizeof(*info));
     info->width = m->ad_cam.image_width;
     info->height = m->ad_cam.image_height;
@@ -912,44 +1084,15 @@ gs_status gs_multi_adapt_info(const gs_multi* m, gs_adapt_info* info) {
 gs_status gs_multi_adapt_maps(gs_multi* m, uint32_t* samples, float* rel_error) {
     if (!m) return fail(GS_ERR_ARG, "null context");
     std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open");
-    DeviceGuard guard;
-    std::vector<uint8_t> packed((size_t)m->cap * 4);
-    for (int i = 0; i < (int)m->dev.size(); i++) {
-        Device& d = m->dev[i];
-        HIPOK(hipSetDevice(d.id));
-        HIPOK(hipStreamSynchronize(d.stream));
-        if (samples) {
-            HIPOK(hipMemcpy(packed.data(), d.map_samples.p, packed.size(), hipMemcpyDeviceToHost));
-            m->permute_rank(i, m->ad_cam, (uint8_t*)samples, packed.data(), 4, true);
-        }
-        if (rel_error) {
-            HIPOK(hipMemcpy(packed.data(), d.map_error.p, packed.size(), hipMemcpyDeviceToHost));
-            m->permute_rank(i, m->ad_cam, (uint8_t*)rel_error, packed.data(), 4, true);
-        }
-    }
-    return GS_OK;
+    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    return m->adapt_maps(samples, rel_error);
 }
 
 gs_status gs_multi_adapt_download(gs_multi* m, double* sums, uint32_t* state) {
     if (!m || !sums || !state) return fail(GS_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open");
-    DeviceGuard guard;
-    std::vector<uint8_t> packed((size_t)m->cap * 40);
-    for (int i = 0; i < (int)m->dev.size(); i++) {
-        Device& d = m->dev[i];
-        const size_t rc = (size_t)m->rank_cap(i, m->ad_cam);
-        const GsRoundLayout l = gs_round_layout(rc, m->ad_R);
-        if (rc == 0) continue;
-        HIPOK(hipSetDevice(d.id));
-        HIPOK(hipStreamSynchronize(d.stream));
-        HIPOK(hipMemcpy(packed.data(), (const char*)d.rstate.p + l.pstate, rc * 40, hipMemcpyDeviceToHost));
-        m->permute_rank(i, m->ad_cam, (uint8_t*)sums, packed.data(), 40, true);
-        HIPOK(hipMemcpy(packed.data(), (const char*)d.rstate.p + l.batches, rc * 4, hipMemcpyDeviceToHost));
-        m->permute_rank(i, m->ad_cam, (uint8_t*)state, packed.data(), 4, true);
-    }
-    return GS_OK;
+    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    return m->adapt_download(sums, state);
 }
 
 gs_status gs_multi_adapt_upload(gs_multi* m, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
@@ -959,68 +1102,109 @@ gs_status gs_multi_adapt_upload(gs_multi* m, const gs_camera* cam, const gs_samp
     std::lock_guard<std::mutex> lock(m->mu);
     gs_status s = m->adapt_begin(cam, ss, seed);
     if (s != GS_OK) return s;
-    auto bail = [&](gs_status st) {
-        m->adapt_end();
-        return st;
-    };
-    if (rounds_done > m->ad_R) return bail(fail(GS_ERR_ARG, "rounds_done exceeds the settings' rounds"));
-    // every pixel's word against rounds_done: an active pixel has taken every round so far, a
-    // stopped one at least one and no more than that
-    const uint64_t npx = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
-    uint64_t active = 0, total = 0, most = 0;
-    for (uint64_t k = 0; k < npx; k++) {
-        const uint32_t nb = state[k] & ~GS_ADAPT_STOPPED;
-        const bool stopped = (state[k] & GS_ADAPT_STOPPED) != 0;
-        if (stopped ? (nb < 1 || nb > rounds_done) : (nb != rounds_done || (rounds_done == m->ad_R && rounds_done)))
-            return bail(fail(GS_ERR_ARG, "a pixel's state disagrees with rounds_done"));
-        active += stopped ? 0u : 1u;
-        total += (uint64_t)nb * ss->batch_size;
-        most = std::max<uint64_t>(most, (uint64_t)nb * ss->batch_size);
-    }
-    if (rounds_done == 0) {  // (nothing to fill: the first pass initialises the state)
-        m->ad_counters = m->ad_base = *counters;
-        return GS_OK;
-    }
-    DeviceGuard guard;
-    std::vector<double> psums((size_t)m->cap * 5);
-    std::vector<uint32_t> words((size_t)m->cap), list;
-    for (int i = 0; i < (int)m->dev.size(); i++) {
-        Device& d = m->dev[i];
-        const size_t cap = (size_t)m->rank_cap(i, *cam);  // (the rank's own: its launches lay the state out for it)
-        const GsRoundLayout l = gs_round_layout(cap, m->ad_R);
-        if (cap == 0) continue;
-        std::fill(psums.begin(), psums.end(), 0.0);
-        std::fill(words.begin(), words.end(), GS_ADAPT_STOPPED);  // (padding: never active)
-        m->permute_rank(i, *cam, (uint8_t*)const_cast<double*>(sums), (uint8_t*)psums.data(), 40, false);
-        m->permute_rank(i, *cam, (uint8_t*)const_cast<uint32_t*>(state), (uint8_t*)words.data(), 4, false);
-        // the round's active list, rebuilt in packed order (its order is scheduling only)
-        list.clear();
-        for (size_t k = 0; k < cap; k++) {
-            if (!(words[k] & GS_ADAPT_STOPPED)) list.push_back((uint32_t)k);
-            if (words[k] == GS_ADAPT_STOPPED) words[k] = 0u;
-        }
-        const uint32_t n_act = (uint32_t)list.size();
-        char* blob = (char*)d.rstate.p;
-        if (hipSetDevice(d.id) != hipSuccess ||
-            hipMemcpy(blob + l.pstate, psums.data(), cap * 40, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(blob + l.batches, words.data(), cap * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            (n_act && hipMemcpy(blob + l.list[rounds_done & 1u], list.data(), (size_t)n_act * 4, hipMemcpyHostToDevice) !=
-                          hipSuccess) ||
-            hipMemcpy(blob + l.counts + (size_t)rounds_done * 4, &n_act, 4, hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(GS_ERR_HIP, "uploading the round state failed"));
-    }
-    m->ad_rounds = rounds_done;
-    m->ad_active = active;
-    m->ad_samples_total = total;
-    m->ad_samples_max = most;
-    m->ad_counters = m->ad_base = *counters;
-    return GS_OK;
+    return m->adapt_fill(rounds_done, sums, state, counters);
 }
 
 gs_status gs_multi_adapt_end(gs_multi* m) {
     if (!m) return fail(GS_ERR_ARG, "null context");
     std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open");
+    m->adapt_end();
+    return GS_OK;
+}
+
+// ---- adaptive views: the adaptation's calls on the tall frame
+// The views' rules and the settings' rules, on the arguments alone; the tall frame's camera.
+static gs_status views_adapt_check(const gs_multi* m, const gs_view* views, uint32_t n_views,
+                                   const gs_sample_settings* ss, gs_camera* tall) {
+    if (!ss) return fail(GS_ERR_ARG, "null argument");
+    gs_status s = gs_views_check(m->dev[0].scene, views, n_views, 1, 1, tall);  // (one chunk: the views' own rules)
+    if (s == GS_OK) s = adapt_settings_check(ss);
+    return s;
+}
+
+gs_status gs_multi_views_adapt_begin(gs_multi* m, const gs_view* views, uint32_t n_views, const gs_sample_settings* ss) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    gs_camera tall;
+    const gs_status s = views_adapt_check(m, views, n_views, ss, &tall);
+    if (s != GS_OK) return s;
+    return m->adapt_begin(&tall, ss, 0, views, n_views);
+}
+
+gs_status gs_multi_views_adapt_pass(gs_multi* m, uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open: gs_multi_views_adapt_begin first");
+    return m->adapt_pass(rounds, out, stats);
+}
+
+gs_status gs_multi_views_adapt_info(gs_multi* m, gs_views_adapt_info* info, uint64_t* view_active_out) {
+    if (!m || !info) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open");
+    const uint32_t nv = (uint32_t)m->vd_views.size();
+    std::memset(info, 0, sizeof(*info));
+    info->width = m->ad_cam.image_width;
+    info->height = m->vd_views[0].cam.image_height;
+    info->n_views = nv;
+    info->tile_h = m->th;
+    info->batch = m->ad_ss.batch_size;
+    info->rounds = m->ad_rounds;
+    info->max_rounds = m->ad_R;
+    info->finished = m->adapt_finished() ? 1u : 0u;
+    info->active_pixels = m->ad_active;
+    info->samples_total = m->ad_samples_total;
+    info->samples_max = m->ad_samples_max;
+    info->counters = m->ad_counters;
+    if (view_active_out) {  // (not hot: the state words cross to the host)
+        const size_t vpx = (size_t)info->width * (size_t)info->height;
+        if (m->ad_rounds == 0) {
+            for (uint32_t v = 0; v < nv; v++) view_active_out[v] = vpx;
+            return GS_OK;
+        }
+        std::vector<uint32_t> state(vpx * nv);
+        const gs_status s = m->adapt_download(nullptr, state.data());
+        if (s != GS_OK) return s;
+        for (uint32_t v = 0; v < nv; v++) {
+            uint64_t act = 0;
+            for (size_t k = 0; k < vpx; k++) act += (state[v * vpx + k] & GS_ADAPT_STOPPED) ? 0u : 1u;
+            view_active_out[v] = act;
+        }
+    }
+    return GS_OK;
+}
+
+gs_status gs_multi_views_adapt_maps(gs_multi* m, uint32_t* samples, float* rel_error) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open");
+    return m->adapt_maps(samples, rel_error);
+}
+
+gs_status gs_multi_views_adapt_download(gs_multi* m, double* sums, uint32_t* state) {
+    if (!m || !sums || !state) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open");
+    return m->adapt_download(sums, state);
+}
+
+gs_status gs_multi_views_adapt_upload(gs_multi* m, const gs_view* views, uint32_t n_views, const gs_sample_settings* ss,
+                                      uint32_t rounds_done, const double* sums, const uint32_t* state,
+                                      const gs_counters* counters) {
+    if (!m || !sums || !state || !counters) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    gs_camera tall;
+    gs_status s = views_adapt_check(m, views, n_views, ss, &tall);
+    if (s == GS_OK) s = m->adapt_begin(&tall, ss, 0, views, n_views);
+    if (s != GS_OK) return s;
+    return m->adapt_fill(rounds_done, sums, state, counters);
+}
+
+gs_status gs_multi_views_adapt_end(gs_multi* m) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open");
     m->adapt_end();
     return GS_OK;
 }

@@ -9,6 +9,9 @@
   preview, per-pixel sample-count and error maps, checkpoint, resume (bit-identical too).
 * ``ViewsProgressiveRenderer`` — a batch of cameras refined in passes, view by view: per-view
   sample budgets and change, preview, checkpoint, resume (each view bit-identical to its own render).
+* ``ViewsAdaptiveRenderer`` / ``render_views_adaptive`` — a batch of cameras under one set of
+  adaptive SampleSettings, in batch rounds whose active lists hold every view's surviving pixels
+  (each view bit-identical to its own adaptive render).
 * ``Renderer`` — device-resident scene for repeated / multi-GPU rendering: upload once,
   render this rank's tiles into a caller-provided device buffer on a given stream.
   Used by bench.py with torch tensors as the device buffers (torch is plumbing only).
@@ -62,7 +65,8 @@ def _launch(num_gpus, tile, plan, devices):
     if devices is not None:
         dev = (C.c_int32 * len(devices))(*devices)
         num_gpus = len(devices)
-    launch = N.gs_launch(num_gpus=num_gpus, tile_w=tile, tile_h=tile, plan=1 if plan else 0,
+    tile_w, tile_h = tile if isinstance(tile, (tuple, list)) else (tile, tile)  # (an int: square tiles)
+    launch = N.gs_launch(num_gpus=num_gpus, tile_w=tile_w, tile_h=tile_h, plan=1 if plan else 0,
                          devices=C.cast(dev, C.c_void_p) if dev is not None else None)
     return launch, dev
 
@@ -200,6 +204,40 @@ class MultiRenderer:
             if k in res:
                 res[k] = res[k].reshape(V, H, W, 3)
         res["counters"] = st.counters.as_dict()
+        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+        return res
+
+    def render_views_adaptive(self, cameras, seeds=None, settings=None, rgb=True, rgb8=False):
+        """V cameras of the context's world under one set of adaptive SampleSettings (default: the
+        scene's), run to the end in batch rounds on the tall frame (gs_multi_views_adapt_*: one
+        begin, one pass of every round, end).  View v's frames are bit for bit those of an adaptive
+        render of cameras[v] alone with seed seeds[v] (default 1).  Returns a dict like
+        render_views(): "rgb" [V,H,W,3] f32, "rgb8", the summed "counters", "stats"."""
+        cams = [camera(c) for c in cameras]
+        V = len(cams)
+        seeds = [1] * V if seeds is None else list(seeds)
+        if len(seeds) != V:
+            raise ValueError("one seed per camera")
+        views = (N.gs_view * max(V, 1))()
+        for v in range(V):
+            views[v].cam = cams[v]
+            views[v].seed = seeds[v]
+        ss = self.settings if settings is None else settings
+        N.check(N.lib.gs_multi_views_adapt_begin(self.handle, views, V, C.byref(ss)))
+        try:
+            W, H = cams[0].image_width, cams[0].image_height
+            out, res, _ = _outputs(W, V * H, rgb, rgb8, False)
+            st = N.gs_stats()
+            N.check(N.lib.gs_multi_views_adapt_pass(self.handle, ss.max_samples // ss.batch_size + 1,
+                                                    C.byref(out) if out is not None else None, C.byref(st)))
+            i = N.gs_views_adapt_info()
+            N.check(N.lib.gs_multi_views_adapt_info(self.handle, C.byref(i), None))
+        finally:
+            N.lib.gs_multi_views_adapt_end(self.handle)
+        for k in ("rgb", "rgb8"):
+            if k in res:
+                res[k] = res[k].reshape(V, H, W, 3)
+        res["counters"] = i.counters.as_dict()
         res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
         return res
 
@@ -847,6 +885,214 @@ class ViewsProgressiveRenderer:
             self.close()
         except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
             pass
+
+
+class ViewsAdaptiveRenderer:
+    """A batch of cameras of one world under ONE set of adaptive SampleSettings, in passes of batch
+    rounds on the tall frame (gs_multi_views_adapt_*): round r renders batch r of every pixel of
+    every view that is still active, so a late round's few surviving pixels of all views share one
+    launch; every pass returns all V frames resolved so far.
+
+    The contract: whatever the number and order of the views, the other cameras, the split into
+    passes, the GPU count, the tile size or a save() / resume() in between, view v's finished frame,
+    rgb8 bytes, sample_counts() and error_map() are bit for bit those of AdaptiveRenderer / render()
+    of cameras[v] alone with seed seeds[v] and the same settings, and the cumulative counters are
+    the sums of those V renders' counters; after k rounds every view shows what AdaptiveRenderer
+    shows for it after k rounds.
+
+    cameras: gs_camera_specs of one width and height; seeds: one per camera (default 1 each);
+    settings: a gs_sample_settings (default: the scene's own).  The scene's own camera is not used."""
+
+    def __init__(self, scene, cameras, seeds=None, settings=None, num_gpus=1, tile=64, devices=None, _resume=None):
+        self.scene = scene
+        self._cams = [camera(c) for c in cameras]
+        V = len(self._cams)
+        self.seeds = [1] * V if seeds is None else [int(s) for s in seeds]
+        if len(self.seeds) != V:
+            raise ValueError("one seed per camera")
+        self.settings = scene.settings if settings is None else settings
+        self._views = (N.gs_view * max(V, 1))()
+        for v in range(V):
+            self._views[v].cam = self._cams[v]
+            self._views[v].seed = self.seeds[v]
+        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices)
+        self._open = False
+        try:
+            if _resume is None:
+                N.check(N.lib.gs_multi_views_adapt_begin(self._mr.handle, self._views, V, C.byref(self.settings)))
+            else:
+                sums, state, meta = _resume
+                cnt = N.gs_counters(**meta["counters"])
+                N.check(N.lib.gs_multi_views_adapt_upload(self._mr.handle, self._views, V, C.byref(self.settings),
+                                                          meta["rounds"], sums.ctypes.data, state.ctypes.data,
+                                                          C.byref(cnt)))
+            self._open = True
+            i = self._info()
+            self.n_views, self.width, self.height = i.n_views, i.width, i.height
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def devices(self):
+        return self._mr.devices
+
+    def _info(self, active=None):
+        i = N.gs_views_adapt_info()
+        N.check(N.lib.gs_multi_views_adapt_info(self._mr.handle, C.byref(i),
+                                                active.ctypes.data if active is not None else None))
+        return i
+
+    @property
+    def finished(self):
+        return bool(self._info().finished)
+
+    def info(self):
+        """width, height (of one view), n_views, tile_h, batch, rounds, max_rounds, finished,
+        active_pixels, samples_total, samples_max (over the batch), the cumulative counters, and
+        "active_fractions": per view, the share of its pixels still active (counted on the host
+        from the downloaded state: not for a hot loop)."""
+        act = np.zeros(max(len(self._cams), 1), dtype=np.uint64)
+        d = self._info(act).as_dict()
+        d["active_fractions"] = [float(a) / (self.width * self.height) for a in act[:len(self._cams)]]
+        return d
+
+    def render_rounds(self, n, rgb=True, rgb8=False):
+        """Render the next `n` rounds (clipped to what remains; none once finished) and resolve all
+        V frames.  Returns a dict: the requested outputs ("rgb" [V,H,W,3] f32, "rgb8"; with none the
+        f32 frames stay on the first device, frame_ptr()), this pass's "counters" and "stats", and
+        "info" (the batch totals after the pass, without the per-view fractions)."""
+        V, W, H = len(self._cams), self.width, self.height
+        out, res, _ = _outputs(W, V * H, rgb, rgb8, False)
+        st = N.gs_stats()
+        N.check(N.lib.gs_multi_views_adapt_pass(self._mr.handle, int(n), C.byref(out) if out is not None else None,
+                                                C.byref(st)))
+        for k in ("rgb", "rgb8"):
+            if k in res:
+                res[k] = res[k].reshape(V, H, W, 3)
+        res["counters"] = st.counters.as_dict()
+        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+        res["info"] = self._info().as_dict()
+        return res
+
+    def render_until(self, rounds=None, seconds=None, active_fraction=None, pass_rounds=1, on_pass=None):
+        """Run passes of `pass_rounds` rounds until the first bound is reached: `rounds` rounds have
+        run in all, `seconds` of wall time have passed since the call, at most `active_fraction`
+        of the batch's pixels are still active -- or, at the latest, the batch is finished.
+        on_pass(info, frames) is called after every pass with the batch totals and the resolved
+        [V,H,W,3] f32 frames.  Returns (info, frames) of the last pass; frames is None when no pass
+        ran."""
+        step = max(1, int(pass_rounds))
+        t0 = time.monotonic()
+        info, frames = self._info().as_dict(), None
+        npx = self.width * self.height * len(self._cams)
+        while not info["finished"]:
+            n = step
+            if rounds is not None:
+                n = min(n, int(rounds) - info["rounds"])
+                if n <= 0:
+                    break
+            if seconds is not None and frames is not None and time.monotonic() - t0 >= seconds:
+                break
+            res = self.render_rounds(n)
+            info, frames = res["info"], res["rgb"]
+            if on_pass is not None:
+                on_pass(info, frames)
+            if active_fraction is not None and info["active_pixels"] <= active_fraction * npx:
+                break
+        return info, frames
+
+    def sample_counts(self):
+        """[V, H, W] u32: the samples every pixel has taken so far (multiples of the batch size)."""
+        out = np.zeros((len(self._cams), self.height, self.width), dtype=np.uint32)
+        N.check(N.lib.gs_multi_views_adapt_maps(self._mr.handle, out.ctypes.data, None))
+        return out
+
+    def error_map(self):
+        """[V, H, W] f32: what the stop test compares with the tolerance (AdaptiveRenderer.error_map)."""
+        out = np.zeros((len(self._cams), self.height, self.width), dtype=np.float32)
+        N.check(N.lib.gs_multi_views_adapt_maps(self._mr.handle, None, out.ctypes.data))
+        return out
+
+    def state(self):
+        """(sums [V, H, W, 5] f64: Σr, Σg, Σb, Σlum, Σlum²; state [V, H, W] u32: batches taken, the
+        top bit once the pixel has stopped) in image order, copies on the host."""
+        V = len(self._cams)
+        sums = np.zeros((V, self.height, self.width, 5), dtype=np.float64)
+        state = np.zeros((V, self.height, self.width), dtype=np.uint32)
+        N.check(N.lib.gs_multi_views_adapt_download(self._mr.handle, sums.ctypes.data, state.ctypes.data))
+        return sums, state
+
+    def frame_ptr(self):
+        """(device pointer of the last resolved [V,H,W,3] f32 frames or None, its device id)."""
+        return self._mr.frame_ptr()
+
+    def scene_info(self, rank=0):
+        return self._mr.scene_info(rank)
+
+    def save(self, path):
+        """Write a checkpoint (grayshift_amd.checkpoint, format 4): the sums and state words, the
+        rounds run, the settings, the views' seeds and gs_camera bytes, the view size and the
+        cumulative counters."""
+        i = self._info()
+        ss = self.settings
+        sums, state = self.state()
+        meta = {"rounds": i.rounds, "seeds": self.seeds, "cameras": [bytes(c) for c in self._cams],
+                "width": i.width, "height": i.height, "confidence": ss.confidence, "tolerance": ss.tolerance,
+                "batch_size": ss.batch_size, "max_samples": ss.max_samples, "counters": i.counters.as_dict()}
+        checkpoint.write_views_adaptive_checkpoint(path, sums, state, meta)
+
+    @classmethod
+    def resume(cls, scene, path, cameras, seeds=None, settings=None, **kw):
+        """Continue the checkpoint at `path` on `scene` with the batch `cameras`: **kw as for the
+        constructor (any device count or tile size).  seeds default to the checkpoint's, settings
+        to the scene's; the checkpoint is rejected (checkpoint.CheckpointError) when its view
+        count, view size, seeds, SampleSettings or gs_camera bytes differ from the batch's.  Whether
+        `scene` is otherwise the world the checkpoint was rendered from is the caller's
+        responsibility."""
+        sums, state, meta = checkpoint.read_views_adaptive_checkpoint(path)
+        cams = [camera(c) for c in cameras]
+        seeds = meta["seeds"] if seeds is None else list(seeds)
+        settings = scene.settings if settings is None else settings
+        W, H = (cams[0].image_width, cams[0].image_height) if cams else (0, 0)
+        checkpoint.check_views_adaptive_compatible(meta, W, H, settings, seeds, [bytes(c) for c in cams])
+        return cls(scene, cameras, seeds=seeds, settings=settings, _resume=(sums, state, meta), **kw)
+
+    def close(self):
+        mr = getattr(self, "_mr", None)
+        if mr is not None:
+            if self._open and mr.handle:
+                N.lib.gs_multi_views_adapt_end(mr.handle)
+            self._open = False
+            mr.close()
+            self._mr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
+            pass
+
+
+def render_views_adaptive(scene, cameras, seeds=None, settings=None, num_gpus=1, tile=64, devices=None, rgb=True,
+                          rgb8=False, maps=False):
+    """A batch of cameras under adaptive settings, run to the end in one call
+    (ViewsAdaptiveRenderer): upload `scene`, run every round, free it.  Returns a dict: "rgb"
+    [V,H,W,3] f32, "rgb8", the cumulative "counters", "info", and with maps=True "samples" and
+    "rel_error" ([V,H,W])."""
+    with ViewsAdaptiveRenderer(scene, cameras, seeds=seeds, settings=settings, num_gpus=num_gpus, tile=tile,
+                               devices=devices) as r:
+        res = r.render_rounds(r._info().max_rounds, rgb=rgb, rgb8=rgb8)
+        res["counters"] = res["info"]["counters"]
+        if maps:
+            res["samples"], res["rel_error"] = r.sample_counts(), r.error_map()
+        return res
 
 
 def ppm_encode_async(d_rgb8, width, height, d_text, text_capacity, d_len, d_scratch, scratch_bytes, stream=0):

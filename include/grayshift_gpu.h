@@ -672,8 +672,8 @@ gs_status gs_multi_adapt_end(gs_multi* m);
  * the size: lanes of one wave may hold different views, with and without defocus, of different
  * max_depth.
  *
- * Fixed spp only (no adaptive settings or PPM text over views; progressive passes over views,
- * view by view, are "Progressive views" below).  A scene that
+ * These calls are fixed spp, without PPM text (progressive passes over views, view by view, are
+ * "Progressive views" below; a batch under adaptive settings is "Adaptive views").  A scene that
  * needs the catch-all kernel (compositions beyond the reference scenes': gs_scene_info.feat & 512)
  * returns GS_ERR_UNSUPPORTED: that kernel has no views form.
  *
@@ -809,6 +809,99 @@ gs_status gs_multi_views_accum_download(gs_multi* m, double* sums);
 gs_status gs_multi_views_accum_upload(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk,
                                       const uint32_t* view_samples, const double* sums, const gs_counters* counters);
 gs_status gs_multi_views_accum_end(gs_multi* m);
+
+/* ---- Adaptive views (additive: the ABI stays 11, no existing call changes) ----
+ * A batch of views under adaptive settings: V views (all W x H) of one device-resident scene and
+ * ONE gs_sample_settings (max_samples >= batch_size) for the batch, run in batch rounds ("Progressive
+ * adaptive passes" above: bs, R, the round state) on the tall frame W x (V H), view v in rows
+ * [v H, (v + 1) H).  A round's active list holds the surviving pixels of every view, so a round is
+ * one parameter kernel, one megakernel and one fold for the whole batch, and a wave of a late round
+ * may hold pixels of several views.
+ *
+ * The contract:
+ *  1. Rounds rendered in passes of r_1, r_2, ... rounds until no pixel of any view is active (at
+ *     the latest after R rounds) leave, for every view v, the linear f32 frame, the rgb8 bytes, the
+ *     `samples` map and the `rel_error` map of a one-shot adaptive render of views[v].cam with seed
+ *     views[v].seed and the same settings (gs_render / gs_multi_adapt_* run to the end), bit for
+ *     bit, and cumulative counters that are the exact sums of those V renders' counters.  The number
+ *     of views, their order, the other cameras in the batch, the split into passes, the rank count,
+ *     the tile size, gs_set_tuning's sample chunk, the partial budget (the segment count) and a
+ *     checkpoint move no bit: sample s of pixel p of a view draws from stream_seed(seed, p, s) with p
+ *     the pixel's index in its own W x H frame, the fold adds a pixel's samples in sample order, and
+ *     the stop test reads that pixel's sums alone -- everything else is scheduling.
+ *  2. After k rounds every view shows what gs_multi_adapt_* shows for it after k rounds (item 2 of
+ *     that contract), `pixels` counting the stopped pixels of all views.
+ *  3. Maps and state cross to the host in image order, view after view: `samples` and `rel_error`
+ *     [V][H][W], `sums` [V][H][W][5] f64 and `state` [V][H][W] u32 (GS_ADAPT_STOPPED), and an upload
+ *     of these continues to the same bits on any rank count.
+ *
+ * Tiles never straddle a view (the tile height is gs_views_tile_h(H, tile_h)) and are assigned
+ * round-robin, as in gs_multi_render_views.  A scene that needs the catch-all kernel
+ * (gs_scene_info.feat & 512) returns GS_ERR_UNSUPPORTED: that kernel has no views form.  The
+ * rounds run on instantiations of their own: the fixed kernel's sample loop over the round's split
+ * items where the scene has neither media nor BVHs under instances, else the loop's kernel with
+ * per-sample items.  A library built with GS_USE_RSPLIT 0 (an A/B switch) has only the second
+ * kind, and returns GS_ERR_UNSUPPORTED for scenes of the first.
+ *
+ * Out of scope: per-view settings (one gs_sample_settings per batch: the rounds share one batch
+ * size and one R); per-pass view selection (every active pixel of every view takes every round);
+ * a views form of the catch-all kernel; cost-planned tiles for batches (the cost pilot is a
+ * one-camera notion); PPM text over views.
+ *
+ * The tile-level primitive, stateless, the sibling of gs_render_tiles_rounds_async: renders rounds
+ * [first_round, first_round + rounds) of this rank's packed pixels of the tall frame on the state
+ * in d_state, at least gs_round_state_bytes(tall camera, part, ss) bytes (the tall camera: view 0's
+ * with image_height = V H); first_round == 0 initialises it.  Outputs as there, per packed pixel.
+ * views: host array, read before the call returns.  GS_ERR_ARG, before any device work and with a
+ * gs_last_error message: the views rules (a NULL pointer -- d_counters may be --, n_views == 0,
+ * views that differ in width or height, any max_depth == 0, V W H not fitting 32 bits, a tile_h that
+ * does not divide H) and the adaptation rules (rounds == 0, batch_size == 0, max_samples <
+ * batch_size, R > 65536, first_round + rounds > R, state_bytes too small, one pixel's batch over
+ * the partial budget).  Where the scene's placement pilot has not run yet it runs with view 0's
+ * camera; it never changes a result. */
+gs_status gs_render_tiles_views_rounds_async(const gs_device_scene* scene, const gs_view* views, uint32_t n_views,
+                                             const gs_sample_settings* ss, const gs_partition* part,
+                                             uint32_t first_round, uint32_t rounds, void* d_state, int64_t state_bytes,
+                                             const gs_round_outputs* out, gs_counters* d_counters, void* stream);
+
+/* The frame context's views adaptation: gs_multi_adapt_* on the tall frame.  _begin fixes the views
+ * and the settings, cuts the tall frame round-robin into tile_w x gs_views_tile_h(H, tile_h) tiles
+ * and allocates the round state on every rank.  Each _pass renders the next `rounds` rounds (clipped
+ * to what remains; none once no pixel is active) and delivers all V frames like
+ * gs_multi_render_views: out->rgb / out->rgb8 are [V][H][W][3] (ppm_text must be NULL), NULL `out`
+ * leaves them on the first device (gs_multi_frame).  While it is open gs_multi_render,
+ * gs_multi_render_views and the three other _begin calls return GS_ERR_ARG, and
+ * gs_multi_views_adapt_begin does while an accumulation, an adaptation or a views accumulation is
+ * open; the gs_multi_adapt_* calls do not see it, and calls without an open views adaptation return
+ * GS_ERR_ARG.  _end closes it and frees the state (gs_multi_destroy does too). */
+typedef struct gs_views_adapt_info {
+    int32_t width, height;   /* of one view */
+    uint32_t n_views;
+    int32_t tile_h;          /* gs_views_tile_h(height, the context's tile height) */
+    uint32_t batch;          /* batch_size */
+    uint32_t rounds;         /* rounds run so far */
+    uint32_t max_rounds;     /* R */
+    uint32_t finished;       /* 1: no pixel of any view is active */
+    uint64_t active_pixels;  /* over all views */
+    uint64_t samples_total;  /* Σ over all pixels of the samples taken: equals counters.paths */
+    uint64_t samples_max;    /* the most samples any pixel has taken */
+    gs_counters counters;    /* cumulative; `pixels` counts the stopped pixels */
+} gs_views_adapt_info;
+gs_status gs_multi_views_adapt_begin(gs_multi* m, const gs_view* views, uint32_t n_views,
+                                     const gs_sample_settings* ss);
+gs_status gs_multi_views_adapt_pass(gs_multi* m, uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats);
+/* view_active_out (V u64, nullable): the active pixels of each view, counted on the host from the
+ * downloaded state words -- not hot. */
+gs_status gs_multi_views_adapt_info(gs_multi* m, gs_views_adapt_info* info, uint64_t* view_active_out);
+/* The maps as [V][H][W] host arrays; either may be NULL.  Before the first pass every value is 0. */
+gs_status gs_multi_views_adapt_maps(gs_multi* m, uint32_t* samples, float* rel_error);
+/* Checkpoints: `sums` [V][H][W][5] f64, `state` [V][H][W] u32.  _upload opens a views adaptation
+ * like _begin and fills it; GS_ERR_ARG when a pixel's state disagrees with rounds_done. */
+gs_status gs_multi_views_adapt_download(gs_multi* m, double* sums, uint32_t* state);
+gs_status gs_multi_views_adapt_upload(gs_multi* m, const gs_view* views, uint32_t n_views,
+                                      const gs_sample_settings* ss, uint32_t rounds_done, const double* sums,
+                                      const uint32_t* state, const gs_counters* counters);
+gs_status gs_multi_views_adapt_end(gs_multi* m);
 
 /* Path of the RCCL library gs_render_multi uses (loaded on this call), or NULL. */
 const char* gs_rccl_library(void);
