@@ -25,6 +25,8 @@ pub const GS_REF_TRIANGLE: u32 = 5;
 pub const GS_REF_LIST: u32 = 6;
 pub const GS_REF_INSTANCE: u32 = 7;
 pub const GS_REF_MEDIUM: u32 = 8;
+/// Build-only: the member index in a leaf slot of a gs_bvh_build_async without refs.
+pub const GS_REF_BUILD_MEMBER: u32 = 15;
 pub const GS_ABI_VERSION: i32 = 11;
 pub const fn gs_make_ref(kind: u32, idx: u32) -> u32 { (kind << GS_REF_SHIFT) | (idx & 0x0FFF_FFFF) }
 
@@ -232,6 +234,15 @@ extern "C" {
     pub fn gs_device_free(d_ptr: *mut c_void) -> gs_status;
     pub fn gs_device_upload(d_dst: *mut c_void, host_src: *const c_void, bytes: i64) -> gs_status;
     pub fn gs_device_download(host_dst: *mut c_void, d_src: *const c_void, bytes: i64) -> gs_status;
+    /// BVHNode::from_list on the device, bit for bit (additive, ABI 11).
+    pub fn gs_bvh_node_count(n: u32) -> i64;
+    pub fn gs_bvh_depth(n: u32) -> i32;
+    pub fn gs_bvh_build_work_bytes(n: u32) -> i64;
+    pub fn gs_bvh_build_lds_members() -> u32;
+    pub fn gs_bvh_build_async(d_boxes: *const f64, d_refs: *const u32, n: u32, node_base: u32,
+                              d_nodes: *mut gs_node, d_order: *mut u32, d_work: *mut c_void, work_bytes: i64,
+                              stream: *mut c_void) -> gs_status;
+    pub fn gs_bvh_build_status(d_work: *mut c_void, stream: *mut c_void) -> gs_status;
     pub fn gs_ppm_max_bytes(width: i32, height: i32) -> i64;
     pub fn gs_ppm_scratch_bytes(width: i32, height: i32) -> i64;
     pub fn gs_ppm_encode_async(d_rgb8: *const u8, width: i32, height: i32, d_text: *mut c_char, text_capacity: i64,

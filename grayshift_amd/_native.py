@@ -145,6 +145,20 @@ class gs_stats(C.Structure):
         return d
 
 
+class gs_build_options(C.Structure):
+    """How a spec's BVHs are built (grayshift_host.h): bvh 0 host, 1 device, 2 host order + rebuild."""
+    _fields_ = [("bvh", C.c_int32), ("device_min_members", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class gs_build_info(C.Structure):
+    _fields_ = [("bvhs_device", C.c_uint32), ("bvhs_host", C.c_uint32), ("members_device", C.c_uint64),
+                ("ms_objects", C.c_float), ("ms_boxes", C.c_float), ("ms_device_build", C.c_float),
+                ("ms_download", C.c_float), ("ms_rebuild", C.c_float), ("ms_flatten", C.c_float)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class gs_scene_info(C.Structure):
     _fields_ = [("node_records", C.c_uint32), ("leaf_records", C.c_uint32), ("lds_nodes", C.c_uint32),
                 ("lds_leaves", C.c_uint32), ("lds_quads", C.c_uint32), ("feat", C.c_int32), ("node_steps", C.c_int32),
@@ -253,6 +267,12 @@ SIGNATURES = {
     "gs_device_free": (C.c_int32, [_P]),
     "gs_device_upload": (C.c_int32, [_P, _P, C.c_int64]),
     "gs_device_download": (C.c_int32, [_P, _P, C.c_int64]),
+    "gs_bvh_node_count": (C.c_int64, [C.c_uint32]),
+    "gs_bvh_depth": (C.c_int32, [C.c_uint32]),
+    "gs_bvh_build_work_bytes": (C.c_int64, [C.c_uint32]),
+    "gs_bvh_build_lds_members": (C.c_uint32, []),
+    "gs_bvh_build_async": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_int64, _P]),
+    "gs_bvh_build_status": (C.c_int32, [_P, _P]),
     "gs_render": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64, _P,
                               C.POINTER(gs_stats)]),
     "gs_render_multi": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,
@@ -321,6 +341,10 @@ SIGNATURES = {
     "gs_multi_views_adapt_end": (C.c_int32, [_P]),
     # grayshift_host.h
     "gs_host_scene_from_spec": (C.c_int32, [C.POINTER(gs_scene_spec), C.POINTER(_P)]),
+    "gs_host_scene_from_spec_ex": (C.c_int32, [C.POINTER(gs_scene_spec), C.POINTER(gs_build_options),
+                                               C.POINTER(_P)]),
+    "gs_host_scene_build_info": (C.c_int32, [_P, C.POINTER(gs_build_info)]),
+    "gs_host_bvh_build": (C.c_int32, [_P, C.c_uint32, C.c_uint32, _P, _P]),
     "gs_host_scene_destroy": (C.c_int32, [_P]),
     "gs_host_scene_flat": (_P, [_P]),
     "gs_host_camera": (C.c_int32, [C.POINTER(gs_camera_spec), C.POINTER(gs_camera)]),

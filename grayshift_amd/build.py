@@ -25,6 +25,7 @@ ORACLE_LIB = os.path.join(ORACLE_DIR, "liboracle.so")
 SOURCES = [
     os.path.join(HERE, "csrc", "device", "render.hip"),   # the kernels and their launchers
     os.path.join(HERE, "csrc", "device", "output.hip"),
+    os.path.join(HERE, "csrc", "device", "bvh_build.hip"),  # BVHNode::from_list on the device
     os.path.join(HERE, "csrc", "host", "scene.cpp"),      # flat scene -> device scene
     os.path.join(HERE, "csrc", "host", "launch.cpp"),     # device scene -> launches
     os.path.join(HERE, "csrc", "host", "world.cpp"),

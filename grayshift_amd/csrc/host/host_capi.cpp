@@ -1,4 +1,7 @@
 // host_capi.cpp — gs_scene_spec -> world objects, and the C-ABI of grayshift_host.h.
+#include <hip/hip_runtime_api.h>
+
+#include <chrono>
 #include <cstring>
 #include <fstream>
 #include <string>
@@ -8,11 +11,101 @@
 
 namespace grayshift {
 
+// The default gs_build_options.device_min_members: the measured crossover of the device path
+// against construct_tree, rounded up to a power of two (profiles/bvh_build/bench.txt).
+static const uint32_t kDeviceMinMembers = 8192;
+
+struct NoDevice : std::runtime_error {
+    NoDevice() : std::runtime_error("no HIP device visible") {}
+};
+struct DeviceError : std::runtime_error {  // a gs_status of the device library; its message stands
+    gs_status code;
+    explicit DeviceError(gs_status c) : std::runtime_error("device error"), code(c) {}
+};
+
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+struct DeviceBuffers {  // freed on every path
+    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    ~DeviceBuffers() {
+        for (void* q : p)
+            if (q) gs_device_free(q);
+    }
+};
+
 struct SpecBuilder {
     const gs_scene_spec& s;
     std::vector<TexturePtr> tex;
     std::vector<MaterialPtr> mat;
-    explicit SpecBuilder(const gs_scene_spec& spec) : s(spec) {}
+    gs_build_options opt{};
+    gs_build_info info{};
+    double ms_bvh = 0;  // time inside build_bvh's non-host paths (taken out of ms_objects)
+    explicit SpecBuilder(const gs_scene_spec& spec, const gs_build_options* o = nullptr) : s(spec) {
+        if (o) opt = *o;
+        if (opt.bvh < 0 || opt.bvh > 2) throw std::invalid_argument("gs_build_options.bvh must be 0, 1 or 2");
+        if (opt.device_min_members == 0) opt.device_min_members = kDeviceMinMembers;
+        if (opt.device_min_members < 3) opt.device_min_members = 3;
+        if (opt.bvh == 1) {
+            int ndev = 0;
+            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw NoDevice();
+        }
+    }
+
+    // BVHNode::from_list of the spec: the world and each GS_OBJ_BVH.
+    std::unique_ptr<BVHNode> build_bvh(std::vector<HittablePtr> objects) {
+        if (opt.bvh == 0 || objects.size() < opt.device_min_members || objects.size() >= GS_REF_MASK) {
+            info.bvhs_host++;
+            return BVHNode::construct_tree(std::move(objects));
+        }
+        const auto t_all = std::chrono::steady_clock::now();
+        const uint32_t n = (uint32_t)objects.size();
+        auto t0 = std::chrono::steady_clock::now();
+        std::vector<double> boxes((size_t)n * 6);
+        for (uint32_t i = 0; i < n; i++) {
+            const AABB b = objects[i]->bounding_box();
+            double* o = &boxes[(size_t)i * 6];
+            o[0] = b.x.min; o[1] = b.y.min; o[2] = b.z.min;
+            o[3] = b.x.max; o[4] = b.y.max; o[5] = b.z.max;
+        }
+        info.ms_boxes += (float)ms_since(t0);
+        const size_t n_nodes = (size_t)gs_bvh_node_count(n);
+        std::vector<gs_node> nodes(n_nodes);
+        std::vector<uint32_t> order(n);
+        if (opt.bvh == 2) {
+            t0 = std::chrono::steady_clock::now();
+            bvh_build_boxes(boxes.data(), n, 0, nodes.data(), order.data());
+            info.ms_device_build += (float)ms_since(t0);
+        } else {
+            t0 = std::chrono::steady_clock::now();
+            DeviceBuffers d;
+            const int64_t work = gs_bvh_build_work_bytes(n);
+            auto ok = [](gs_status st) {
+                if (st != GS_OK) throw DeviceError(st);
+            };
+            ok(gs_device_alloc((int64_t)boxes.size() * 8, &d.p[0]));
+            ok(gs_device_alloc((int64_t)n_nodes * (int64_t)sizeof(gs_node), &d.p[1]));
+            ok(gs_device_alloc((int64_t)n * 4, &d.p[2]));
+            ok(gs_device_alloc(work, &d.p[3]));
+            ok(gs_device_upload(d.p[0], boxes.data(), (int64_t)boxes.size() * 8));
+            ok(gs_bvh_build_async((const double*)d.p[0], nullptr, n, 0, (gs_node*)d.p[1], (uint32_t*)d.p[2], d.p[3],
+                                  work, nullptr));
+            ok(gs_bvh_build_status(d.p[3], nullptr));
+            info.ms_device_build += (float)ms_since(t0);
+            t0 = std::chrono::steady_clock::now();
+            ok(gs_device_download(nodes.data(), d.p[1], (int64_t)n_nodes * (int64_t)sizeof(gs_node)));
+            ok(gs_device_download(order.data(), d.p[2], (int64_t)n * 4));
+            info.ms_download += (float)ms_since(t0);
+        }
+        t0 = std::chrono::steady_clock::now();
+        auto tree = BVHNode::from_order(std::move(objects), order.data(), nodes.data());
+        info.ms_rebuild += (float)ms_since(t0);
+        info.bvhs_device++;
+        info.members_device += n;
+        ms_bvh += ms_since(t_all);
+        return tree;
+    }
 
     TexturePtr texture(int idx, int depth = 0) {
         if (idx < 0 || idx >= s.n_textures) throw std::invalid_argument("texture index out of range");
@@ -69,7 +162,7 @@ struct SpecBuilder {
                 for (auto& c : children()) l->add(std::move(c));
                 return l;
             }
-            case GS_OBJ_BVH: return BVHNode::construct_tree(children());
+            case GS_OBJ_BVH: return build_bvh(children());
             case GS_OBJ_TRANSLATE: return std::make_unique<Translate>(object(o.first, depth + 1), Vec3(p[0], p[1], p[2]));
             case GS_OBJ_ROTATE_Y: return std::make_unique<RotateY>(object(o.first, depth + 1), p[0]);
             case GS_OBJ_MEDIUM:
@@ -78,6 +171,7 @@ struct SpecBuilder {
         }
     }
     std::unique_ptr<BVHNode> world() {
+        const auto t_world = std::chrono::steady_clock::now();
         tex.assign(s.n_textures > 0 ? s.n_textures : 0, nullptr);
         for (int i = 0; i < s.n_materials; i++) {
             const gs_material_spec& m = s.materials[i];
@@ -92,7 +186,10 @@ struct SpecBuilder {
         }
         HittableList world;
         for (int i = 0; i < s.n_world; i++) world.add(object(s.world[i]));
-        return BVHNode::from_list(std::move(world));
+        if (world.objects.empty()) throw std::invalid_argument("BVHNode::from_list of an empty list");
+        auto root = build_bvh(std::move(world.objects));  // BVHNode::from_list(world)
+        info.ms_objects = (float)(ms_since(t_world) - ms_bvh);
+        return root;
     }
     Background background() {
         const gs_background_spec& b = s.background;
@@ -133,6 +230,7 @@ using namespace grayshift;
 
 struct gs_host_scene {
     std::unique_ptr<FlatScene> flat;
+    gs_build_info info{};
 };
 
 // The device library owns gs_last_error(); the host reports through it.
@@ -147,6 +245,10 @@ template <class F>
 static gs_status guarded(F&& f) {
     try {
         return f();
+    } catch (const NoDevice& e) {
+        return fail(GS_ERR_NO_DEVICE, e.what());
+    } catch (const DeviceError& e) {
+        return e.code;  // (the device library left its message)
     } catch (const std::domain_error& e) {
         return fail(GS_ERR_UNSUPPORTED, e.what());
     } catch (const std::bad_alloc&) {
@@ -158,15 +260,40 @@ static gs_status guarded(F&& f) {
 
 extern "C" {
 
-gs_status gs_host_scene_from_spec(const gs_scene_spec* spec, gs_host_scene** out) {
+gs_status gs_host_scene_from_spec_ex(const gs_scene_spec* spec, const gs_build_options* options,
+                                     gs_host_scene** out) {
     if (!spec || !out) return fail(GS_ERR_ARG, "null argument");
     return guarded([&]() {
-        SpecBuilder b(*spec);
+        SpecBuilder b(*spec, options);
         auto world = b.world();
         auto bg = b.background();
         auto hs = std::make_unique<gs_host_scene>();
+        const auto t0 = std::chrono::steady_clock::now();
         hs->flat = flatten_world(*world, bg);
+        b.info.ms_flatten = (float)ms_since(t0);
+        hs->info = b.info;
         *out = hs.release();
+        return GS_OK;
+    });
+}
+
+gs_status gs_host_scene_from_spec(const gs_scene_spec* spec, gs_host_scene** out) {
+    return gs_host_scene_from_spec_ex(spec, nullptr, out);
+}
+
+gs_status gs_host_scene_build_info(const gs_host_scene* scene, gs_build_info* out) {
+    if (!scene || !out) return fail(GS_ERR_ARG, "null argument");
+    *out = scene->info;
+    return GS_OK;
+}
+
+gs_status gs_host_bvh_build(const double* boxes, uint32_t n, uint32_t node_base, gs_node* nodes, uint32_t* order) {
+    if (!boxes || !nodes || !order) return fail(GS_ERR_ARG, "gs_host_bvh_build: null pointer");
+    if (n == 0) return fail(GS_ERR_ARG, "gs_host_bvh_build: BVHNode::from_list of an empty list");
+    if (n >= GS_REF_MASK || (uint64_t)node_base + (uint64_t)gs_bvh_node_count(n) > (uint64_t)GS_REF_MASK)
+        return fail(GS_ERR_ARG, "gs_host_bvh_build: node_base + nodes(n) exceeds a 28-bit reference");
+    return guarded([&]() {
+        bvh_build_boxes(boxes, n, node_base, nodes, order);
         return GS_OK;
     });
 }
@@ -270,7 +397,7 @@ int64_t gs_host_struct_size(const char* name) {
     GS_SZ(gs_background) GS_SZ(gs_flat_scene) GS_SZ(gs_camera) GS_SZ(gs_partition)
     GS_SZ(gs_render_outputs) GS_SZ(gs_launch) GS_SZ(gs_multi_outputs) GS_SZ(gs_stats) GS_SZ(gs_scene_info)
     GS_SZ(gs_accum_info) GS_SZ(gs_adapt_info) GS_SZ(gs_round_outputs) GS_SZ(gs_view)
-    GS_SZ(gs_views_accum_info) GS_SZ(gs_views_adapt_info)
+    GS_SZ(gs_views_accum_info) GS_SZ(gs_views_adapt_info) GS_SZ(gs_build_options) GS_SZ(gs_build_info)
 #undef GS_SZ
     return -1;
 }

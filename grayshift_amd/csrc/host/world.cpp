@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <cstring>
 
+#include "bvh_shape.hpp"
+
 namespace grayshift {
 
 AABB AABB::from_corners(const Vec3& a, const Vec3& b) {  // AABB.rs:24-47, pad :123-128
@@ -122,6 +124,92 @@ std::unique_ptr<BVHNode> BVHNode::construct_tree(std::vector<HittablePtr> object
     node->right = construct_tree(std::move(right_objs));
     node->bbox = bbox;
     return node;
+}
+
+static AABB node_box(const gs_node& n) {
+    return AABB(Interval(n.min[0], n.max[0]), Interval(n.min[1], n.max[1]), Interval(n.min[2], n.max[2]));
+}
+
+// The subtree over members order[lo .. lo + n) whose node is node_boxes[idx] (bvh_shape.hpp).
+static std::unique_ptr<BVHNode> subtree_from_order(std::vector<HittablePtr>& objects, const uint32_t* order,
+                                                   const gs_node* node_boxes, size_t lo, size_t n, size_t idx) {
+    auto node = std::make_unique<BVHNode>();
+    node->bbox = node_box(node_boxes[idx]);
+    auto take = [&](size_t pos) {
+        const uint32_t m = order[pos];
+        if (m >= objects.size() || !objects[m]) throw std::logic_error("BVHNode::from_order: not a permutation");
+        return std::move(objects[m]);
+    };
+    if (n == 1) {
+        node->left = take(lo);
+    } else if (n == 2) {
+        node->left = take(lo);
+        node->right = take(lo + 1);
+    } else {
+        const size_t h = n / 2;
+        node->left = subtree_from_order(objects, order, node_boxes, lo, h, idx + 1);
+        node->right = subtree_from_order(objects, order, node_boxes, lo + h, n - h,
+                                         idx + 1 + (size_t)gs_shape_nodes((uint32_t)h));
+    }
+    return node;
+}
+
+std::unique_ptr<BVHNode> BVHNode::from_order(std::vector<HittablePtr> objects, const uint32_t* order,
+                                             const gs_node* node_boxes) {
+    if (objects.empty()) throw std::invalid_argument("BVHNode::from_list of an empty list");
+    if (!order || !node_boxes) throw std::invalid_argument("BVHNode::from_order: null argument");
+    return subtree_from_order(objects, order, node_boxes, 0, objects.size(), 0);
+}
+
+namespace {
+// A member of bvh_build_boxes: its box and its index in the list.
+class BoxMember : public Hittable {
+public:
+    BoxMember(const double* b, uint32_t index)
+        : bbox(Interval(b[0], b[3]), Interval(b[1], b[4]), Interval(b[2], b[5])), index(index) {}
+    AABB bounding_box() const override { return bbox; }
+    uint32_t flatten(Flattener&) const override { throw std::logic_error("BoxMember::flatten"); }
+    AABB bbox;
+    uint32_t index;
+};
+
+struct BoxTreeWriter {
+    uint32_t node_base;
+    gs_node* nodes;
+    uint32_t* order;
+    size_t n_nodes = 0, n_leaves = 0;
+    uint32_t write(const Hittable* h) {
+        if (const BoxMember* m = dynamic_cast<const BoxMember*>(h)) {
+            order[n_leaves++] = m->index;
+            return GS_MAKE_REF(GS_REF_BUILD_MEMBER, m->index);
+        }
+        const BVHNode* b = static_cast<const BVHNode*>(h);
+        const size_t idx = n_nodes++;
+        const uint32_t l = write(b->left.get());
+        const uint32_t r = b->right ? write(b->right.get()) : (uint32_t)GS_REF_NONE;
+        gs_node& n = nodes[idx];
+        std::memset(&n, 0, sizeof(n));
+        n.min[0] = b->bbox.x.min; n.min[1] = b->bbox.y.min; n.min[2] = b->bbox.z.min;
+        n.max[0] = b->bbox.x.max; n.max[1] = b->bbox.y.max; n.max[2] = b->bbox.z.max;
+        n.left = l;
+        n.right = r;
+        return GS_MAKE_REF(GS_REF_NODE, node_base + idx);
+    }
+};
+}  // namespace
+
+void bvh_build_boxes(const double* boxes, uint32_t n, uint32_t node_base, gs_node* nodes, uint32_t* order) {
+    std::vector<HittablePtr> members;
+    members.reserve(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const double* b = boxes + (size_t)i * 6;
+        for (int c = 0; c < 6; c++)
+            if (std::isnan(b[c])) throw std::invalid_argument("BVH sort: NaN bounding box");
+        members.push_back(std::make_unique<BoxMember>(b, i));
+    }
+    auto root = BVHNode::construct_tree(std::move(members));
+    BoxTreeWriter w{node_base, nodes, order};
+    w.write(root.get());
 }
 
 // ---------------------------------------------------------------- flatten

@@ -271,6 +271,12 @@ class BVHNode : public Hittable {
 public:
     static std::unique_ptr<BVHNode> from_list(HittableList list) { return construct_tree(std::move(list.objects)); }
     static std::unique_ptr<BVHNode> construct_tree(std::vector<HittablePtr> objects);
+    // The same object tree from a finished build, in O(n) with no sort and no box fold: `order`
+    // is the member at each leaf position, left to right, and `node_boxes` the tree's nodes in
+    // pre-order (the right child of a node of m members at idx + 1 + nodes(m / 2)); both as
+    // gs_host_bvh_build or the device builder (gs_bvh_build_async) leave them.
+    static std::unique_ptr<BVHNode> from_order(std::vector<HittablePtr> objects, const uint32_t* order,
+                                               const gs_node* node_boxes);
     AABB bounding_box() const override { return bbox; }
     uint32_t flatten(Flattener& f) const override;
     HittablePtr left, right;  // right may be null (n == 1)
@@ -377,6 +383,11 @@ private:
     gs_sample_settings ss{};
     Background bg;
 };
+
+// construct_tree over n bare boxes (double[n][6]: min xyz, max xyz), the product's own code path
+// with a box-only Hittable: the nodes in pre-order (child refs GS_REF_NODE | node_base + idx,
+// a member's leaf slot GS_REF_BUILD_MEMBER | member) and the member at each leaf position.
+void bvh_build_boxes(const double* boxes, uint32_t n, uint32_t node_base, gs_node* nodes, uint32_t* order);
 
 // Flatten a world (the BVH root) for the device.
 std::unique_ptr<FlatScene> flatten_world(const Hittable& world, const Background& bg);

@@ -93,13 +93,14 @@ def _outputs(W, H, rgb, rgb8, ppm):
     return out, res, ppm_buf
 
 
-def render_multi(scene, num_gpus=0, seed=1, tile=64, plan=True, rgb=True, rgb8=False, ppm=False, devices=None):
+def render_multi(scene, num_gpus=0, seed=1, tile=64, plan=True, rgb=True, rgb8=False, ppm=False, devices=None,
+                 bvh="host"):
     """camera.rs:105-114 (and with ppm=True the whole of :100-121) on `num_gpus` GPUs of
     this node (0 = every visible one) through gs_render_multi: one scene per device,
     tiles rendered concurrently, one RCCL gather to the first device.  Returns a dict
     with the requested outputs ("rgb" [H,W,3] f32, "rgb8" [H,W,3] u8, "ppm" bytes), the
     summed "counters" and the call's "stats"."""
-    host = HostScene(scene.spec)
+    host = HostScene(scene.spec, bvh=bvh)
     try:
         cam = camera(scene.camera)
         out, res, ppm_buf = _outputs(cam.image_width, cam.image_height, rgb, rgb8, ppm)
@@ -124,9 +125,9 @@ class MultiRenderer:
     call (plan, render on every device, one gather, unpack).  num_gpus=0: every visible
     device; num_gpus=1: no collective."""
 
-    def __init__(self, scene, num_gpus=1, tile=64, plan=True, devices=None):
+    def __init__(self, scene, num_gpus=1, tile=64, plan=True, devices=None, bvh="host", device_min_members=0):
         self.scene = scene
-        self.host = HostScene(scene.spec)
+        self.host = HostScene(scene.spec, bvh=bvh, device_min_members=device_min_members)
         self.cam = camera(scene.camera)
         self.settings = scene.settings
         launch, _dev = _launch(num_gpus, tile, plan, devices)
@@ -269,13 +270,13 @@ class MultiRenderer:
             pass
 
 
-def render_views(scene, cameras, samples, seeds=None, num_gpus=1, tile=64, devices=None, **kw):
+def render_views(scene, cameras, samples, seeds=None, num_gpus=1, tile=64, devices=None, bvh="host", **kw):
     """MultiRenderer.render_views in one call: upload `scene`, render the cameras, free it.  A
     batch whose chunk sums exceed the partial budget is rendered as consecutive groups of cameras
     that fit, the results concatenated: grouping changes no bit (the views contract).  Returns
     MultiRenderer.render_views' dict; "stats" is then a list, one gs_stats dict per group.
     **kw: render_views' chunk, rgb, rgb8."""
-    r = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices)
+    r = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices, bvh=bvh)
     try:
         cameras = list(cameras)
         seeds = [1] * len(cameras) if seeds is None else list(seeds)
@@ -311,10 +312,11 @@ class ProgressiveRenderer:
     settings have their own pass form, AdaptiveRenderer).  chunk: the coarse sample chunk c (0 = 16); every pass is 1 to
     64 whole chunks."""
 
-    def __init__(self, scene, num_gpus=1, seed=1, chunk=0, tile=64, plan=True, devices=None, _resume=None):
+    def __init__(self, scene, num_gpus=1, seed=1, chunk=0, tile=64, plan=True, devices=None, bvh="host",
+                 _resume=None):
         self.scene = scene
         self.seed = int(seed)
-        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=plan, devices=devices)
+        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=plan, devices=devices, bvh=bvh)
         self._open = False
         self._passes0 = 0
         self._delta0 = 0.0
@@ -484,10 +486,10 @@ class AdaptiveRenderer:
     of render() / render_multi() with the same settings and seed, bit for bit; after k rounds
     the frame is the one-shot frame with max_samples = k * batch_size - 1."""
 
-    def __init__(self, scene, num_gpus=1, seed=1, tile=64, plan=True, devices=None, _resume=None):
+    def __init__(self, scene, num_gpus=1, seed=1, tile=64, plan=True, devices=None, bvh="host", _resume=None):
         self.scene = scene
         self.seed = int(seed)
-        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=plan, devices=devices)
+        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=plan, devices=devices, bvh=bvh)
         self._open = False
         mr = self._mr
         try:
@@ -660,7 +662,8 @@ class ViewsProgressiveRenderer:
     chunk: the coarse sample chunk c (0 = 16), every pass is 1 to 64 whole chunks.  The scene's own
     camera and SampleSettings are not used."""
 
-    def __init__(self, scene, cameras, seeds=None, num_gpus=1, chunk=0, tile=64, devices=None, _resume=None):
+    def __init__(self, scene, cameras, seeds=None, num_gpus=1, chunk=0, tile=64, devices=None, bvh="host",
+                 _resume=None):
         self.scene = scene
         self._cams = [camera(c) for c in cameras]
         V = len(self._cams)
@@ -671,7 +674,7 @@ class ViewsProgressiveRenderer:
         for v in range(V):
             self._views[v].cam = self._cams[v]
             self._views[v].seed = self.seeds[v]
-        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices)
+        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices, bvh=bvh)
         self._open = False
         self._passes0 = 0
         self._deltas0 = None
@@ -903,7 +906,8 @@ class ViewsAdaptiveRenderer:
     cameras: gs_camera_specs of one width and height; seeds: one per camera (default 1 each);
     settings: a gs_sample_settings (default: the scene's own).  The scene's own camera is not used."""
 
-    def __init__(self, scene, cameras, seeds=None, settings=None, num_gpus=1, tile=64, devices=None, _resume=None):
+    def __init__(self, scene, cameras, seeds=None, settings=None, num_gpus=1, tile=64, devices=None, bvh="host",
+                 _resume=None):
         self.scene = scene
         self._cams = [camera(c) for c in cameras]
         V = len(self._cams)
@@ -915,7 +919,7 @@ class ViewsAdaptiveRenderer:
         for v in range(V):
             self._views[v].cam = self._cams[v]
             self._views[v].seed = self.seeds[v]
-        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices)
+        self._mr = MultiRenderer(scene, num_gpus=num_gpus, tile=tile, plan=False, devices=devices, bvh=bvh)
         self._open = False
         try:
             if _resume is None:
@@ -1081,13 +1085,13 @@ class ViewsAdaptiveRenderer:
 
 
 def render_views_adaptive(scene, cameras, seeds=None, settings=None, num_gpus=1, tile=64, devices=None, rgb=True,
-                          rgb8=False, maps=False):
+                          rgb8=False, maps=False, bvh="host"):
     """A batch of cameras under adaptive settings, run to the end in one call
     (ViewsAdaptiveRenderer): upload `scene`, run every round, free it.  Returns a dict: "rgb"
     [V,H,W,3] f32, "rgb8", the cumulative "counters", "info", and with maps=True "samples" and
     "rel_error" ([V,H,W])."""
     with ViewsAdaptiveRenderer(scene, cameras, seeds=seeds, settings=settings, num_gpus=num_gpus, tile=tile,
-                               devices=devices) as r:
+                               devices=devices, bvh=bvh) as r:
         res = r.render_rounds(r._info().max_rounds, rgb=rgb, rgb8=rgb8)
         res["counters"] = res["info"]["counters"]
         if maps:
@@ -1114,10 +1118,19 @@ def write_ppm(path, rgb):
 class HostScene:
     """World + BVHNode::from_list + flat arrays, built by the C++ host mirror."""
 
-    def __init__(self, spec):
+    BVH = {"host": 0, "device": 1, "host-order": 2}  # ("host-order": the rebuild fed by the host, a test seam)
+
+    def __init__(self, spec, bvh="host", device_min_members=0):
+        """bvh: who builds the spec's BVHs (the world and each nested one): "host"
+        (construct_tree) or "device" (gs_bvh_build_async on the current device for lists of
+        at least device_min_members members, 0 = the measured default; the flat scene is
+        byte-identical either way)."""
+        if bvh not in self.BVH:
+            raise ValueError("bvh must be 'host' or 'device', not %r" % (bvh,))
         self._spec = spec
         h = C.c_void_p()
-        N.check(N.lib.gs_host_scene_from_spec(spec.ptr(), C.byref(h)))
+        opt = N.gs_build_options(bvh=self.BVH[bvh], device_min_members=device_min_members)
+        N.check(N.lib.gs_host_scene_from_spec_ex(spec.ptr(), C.byref(opt), C.byref(h)))
         self.handle = h
         self.flat_ptr = N.lib.gs_host_scene_flat(h)
         self.flat = N.gs_flat_scene.from_address(self.flat_ptr)
@@ -1133,6 +1146,13 @@ class HostScene:
         except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
             pass
 
+    def build_info(self):
+        """gs_build_info of this scene's build: BVHs built on the device / the host, members
+        of the device-built ones, and the build's split in ms."""
+        info = N.gs_build_info()
+        N.check(N.lib.gs_host_scene_build_info(self.handle, C.byref(info)))
+        return info.as_dict()
+
     def stats(self):
         f = self.flat
         return {"nodes": f.n_nodes, "spheres": f.n_spheres, "mspheres": f.n_mspheres, "quads": f.n_quads,
@@ -1143,13 +1163,14 @@ class HostScene:
 class Renderer:
     """A scene resident in HBM of the current device, rendered tile-partitioned."""
 
-    def __init__(self, scene, rank=0, world_size=1, tile=64, tile_h=None, plan=False, plan_seed=1, order=None):
+    def __init__(self, scene, rank=0, world_size=1, tile=64, tile_h=None, plan=False, plan_seed=1, order=None,
+                 bvh="host"):
         """plan: cost-balanced tile assignment (gs_plan_tiles: a 1-spp pilot of the whole
         frame on this device) instead of round-robin.  order: a plan computed elsewhere
         (e.g. on rank 0 and broadcast: int32, slots_per_rank * world_size entries, see
         gs_partition.d_tile_order), used as given."""
         self.scene = scene
-        self.host = HostScene(scene.spec)
+        self.host = HostScene(scene.spec, bvh=bvh)
         self.cam = camera(scene.camera)
         self.settings = scene.settings
         self.part = N.gs_partition(rank=rank, world_size=world_size, tile_w=tile, tile_h=tile_h or tile)

@@ -51,7 +51,9 @@ enum gs_ref_kind {
     GS_REF_TRIANGLE = 5, /* Triangle                      -> triangles[] */
     GS_REF_LIST = 6,     /* HittableList of primitives    -> lists[]     */
     GS_REF_INSTANCE = 7, /* Translate / RotateY           -> instances[] */
-    GS_REF_MEDIUM = 8    /* ConstantMedium                -> media[]     */
+    GS_REF_MEDIUM = 8,   /* ConstantMedium                -> media[]     */
+    GS_REF_BUILD_MEMBER = 15 /* build-only: member index of a gs_bvh_build_async without refs; no
+                              * scene may hold it (gs_device_scene_create rejects it) */
 };
 #define GS_MAKE_REF(kind, idx) (((uint32_t)(kind) << GS_REF_SHIFT) | ((uint32_t)(idx) & GS_REF_MASK))
 
@@ -911,6 +913,36 @@ gs_status gs_device_alloc(int64_t bytes, void** d_out);
 gs_status gs_device_free(void* d_ptr);
 gs_status gs_device_upload(void* d_dst, const void* host_src, int64_t bytes);
 gs_status gs_device_download(void* host_dst, const void* d_src, int64_t bytes); /* (ABI 6) synchronous */
+
+/* ---- BVHNode::from_list on the device (additive, ABI 11) ----
+ * The reference's tree (BVH.rs:15-65) draws no random axis: the box is the left fold of the
+ * members' boxes in their current order, the axis is longest_axis(), the sort is stable on
+ * bbox[axis].min and the split is at len / 2.  The shape is therefore a function of n alone --
+ * nodes(n) = 1 if n <= 2 else 1 + nodes(n / 2) + nodes(n - n / 2) -- and the device builds the
+ * host's tree bit for bit (gs_host_bvh_build is the yardstick).
+ *
+ * d_boxes: n member boxes, double[n][6] (min xyz, max xyz) in list order.  d_refs (nullable):
+ * the tagged ref written where member i becomes a leaf; NULL writes GS_REF_BUILD_MEMBER | i.
+ * d_nodes: gs_bvh_node_count(n) nodes in the host flattener's pre-order (the left subtree
+ * follows its parent, the right child of a node of m members sits at idx + 1 + nodes(m / 2));
+ * child refs are GS_REF_NODE | (node_base + idx); pads are zero.  d_order: the member at each
+ * leaf position, left to right.  d_work: gs_bvh_build_work_bytes(n) bytes, 256-byte aligned.
+ *
+ * The call enqueues a fixed sequence of launches (a function of n) on the stream and returns;
+ * nothing is read back between levels and no kernel waits on another block.  A segment of at
+ * most gs_bvh_build_lds_members() members is finished by one workgroup in LDS.  GS_ERR_ARG,
+ * before any device work: a NULL pointer (d_refs may be), n == 0, n or node_base + nodes(n) past
+ * 28 bits, work_bytes too small.  A NaN bound (the host throws) is found on the device:
+ * gs_bvh_build_status waits for the stream and returns GS_ERR_ARG with a message; the outputs
+ * of such a build must not be used. */
+int64_t gs_bvh_node_count(uint32_t n); /* nodes(n); -1 for n == 0 */
+int32_t gs_bvh_depth(uint32_t n);      /* levels of that tree (0 for n == 0) */
+int64_t gs_bvh_build_work_bytes(uint32_t n); /* a function of n alone; -1 for n == 0 */
+uint32_t gs_bvh_build_lds_members(void);
+gs_status gs_bvh_build_async(const double* d_boxes, const uint32_t* d_refs /* nullable */, uint32_t n,
+                             uint32_t node_base, gs_node* d_nodes, uint32_t* d_order, void* d_work,
+                             int64_t work_bytes, void* stream);
+gs_status gs_bvh_build_status(void* d_work, void* stream); /* synchronises; GS_ERR_ARG on NaN */
 
 /* Synchronous full-frame render on the current device: upload, render, copy back.
  * out_rgb: host buffer W*H*3 f32 (linear).  stats: host, nullable (counters, kernel and

@@ -23,6 +23,38 @@ typedef struct gs_host_scene gs_host_scene; /* world + BVH + flat arrays (host m
 /* Build the world from a spec: objects, BVHNode::from_list(world), flatten. */
 gs_status gs_host_scene_from_spec(const gs_scene_spec* spec, gs_host_scene** out);
 gs_status gs_host_scene_destroy(gs_host_scene* scene);
+
+/* How the spec's BVHs (the world and each GS_OBJ_BVH) are built.  bvh: 0 the host's
+ * construct_tree (the default everywhere), 1 the device builder (gs_bvh_build_async on the
+ * current device: the members' boxes go up, the order and the nodes come down, and
+ * BVHNode::from_order rebuilds the object tree in O(n)), 2 the same rebuild fed by
+ * gs_host_bvh_build (a test seam: the host half without a device).  Lists of fewer than
+ * device_min_members members use construct_tree (0: the measured default, DESIGN.md §3;
+ * values below 3 mean 3).  The flattened scene is byte-identical in every mode. */
+typedef struct gs_build_options {
+    int32_t bvh;
+    uint32_t device_min_members;
+    uint32_t pad[2];
+} gs_build_options;
+/* What the last build of a scene did: BVHs built either way, members of the device-built
+ * ones, and the wall time in ms of the world objects (construct_tree of host-built BVHs
+ * included), the members' boxes, the order's build (device, or gs_host_bvh_build under bvh = 2;
+ * upload and allocation included), the download, from_order, and flatten. */
+typedef struct gs_build_info {
+    uint32_t bvhs_device, bvhs_host;
+    uint64_t members_device;
+    float ms_objects, ms_boxes, ms_device_build, ms_download, ms_rebuild, ms_flatten;
+} gs_build_info;
+/* gs_host_scene_from_spec under options (NULL: the defaults).  bvh = 1 without a device:
+ * GS_ERR_NO_DEVICE. */
+gs_status gs_host_scene_from_spec_ex(const gs_scene_spec* spec, const gs_build_options* options,
+                                     gs_host_scene** out);
+gs_status gs_host_scene_build_info(const gs_host_scene* scene, gs_build_info* out);
+/* The host's construct_tree over n bare boxes (double[n][6]: min xyz, max xyz), same code path
+ * as the product with a box-only Hittable; outputs as gs_bvh_build_async without refs writes
+ * them (host memory).  The yardstick of the device builder.  NaN in a box: GS_ERR_ARG. */
+gs_status gs_host_bvh_build(const double* boxes, uint32_t n, uint32_t node_base, gs_node* nodes,
+                            uint32_t* order);
 /* View of the flattened arrays (valid while the scene lives). */
 const gs_flat_scene* gs_host_scene_flat(const gs_host_scene* scene);
 
