@@ -205,6 +205,7 @@ extern "C" {
                                   seed: u64, part: *const gs_partition, d_packed_rgb: *mut f32, d_visits: *mut u32,
                                   stream: *mut c_void) -> gs_status;
     pub fn gs_debug_last_launch_feat(scene: *const gs_device_scene, feat: *mut i32) -> gs_status;
+    pub fn gs_debug_device_scene_record(scene: *const gs_device_scene, out: *mut c_void, out_bytes: i64) -> gs_status;
     pub fn gs_device_scene_create(scene: *const gs_flat_scene, out: *mut *mut gs_device_scene) -> gs_status;
     pub fn gs_device_scene_destroy(scene: *mut gs_device_scene) -> gs_status;
     pub fn gs_device_scene_info(scene: *const gs_device_scene, out: *mut gs_scene_info) -> gs_status;

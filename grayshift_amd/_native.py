@@ -89,6 +89,42 @@ class gs_medium_rec(C.Structure):  # gs_medium (a flat-scene record)
     _fields_ = [("boundary", C.c_uint32), ("material", C.c_uint32), ("density_neg_inv", C.c_double)]
 
 
+# The flat scene's other records (grayshift_gpu.h), for code that walks a gs_flat_scene.
+class gs_node(C.Structure):
+    _fields_ = [("min", D3), ("max", D3), ("left", C.c_uint32), ("right", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class gs_sphere(C.Structure):
+    _fields_ = [("center", D3), ("radius", C.c_double), ("material", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class gs_msphere(C.Structure):
+    _fields_ = [("center_start", D3), ("center_path", D3), ("radius", C.c_double), ("material", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class gs_quad(C.Structure):
+    _fields_ = [("q", D3), ("u", D3), ("v", D3), ("w", D3), ("normal", D3), ("d", C.c_double),
+                ("material", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class gs_triangle(C.Structure):
+    _fields_ = [("a", D3), ("b", D3), ("c", D3), ("normal", D3), ("material", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class gs_instance(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("child", C.c_uint32), ("p", D3)]
+
+
+class gs_material(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("texture", C.c_uint32), ("albedo", D3), ("param", C.c_double)]
+
+
+class gs_texture(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("even", C.c_uint32), ("odd", C.c_uint32), ("image", C.c_uint32),
+                ("color", D3), ("scale_inv", C.c_double)]
+
+
 class gs_partition(C.Structure):
     _fields_ = [("rank", C.c_int32), ("world_size", C.c_int32), ("tile_w", C.c_int32), ("tile_h", C.c_int32),
                 ("d_tile_order", C.c_void_p), ("slots_per_rank", C.c_int32), ("pad", C.c_int32)]
@@ -240,6 +276,7 @@ SIGNATURES = {
     "gs_debug_record_visits": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,
                                            C.POINTER(gs_partition), _P, _P, _P]),
     "gs_debug_last_launch_feat": (C.c_int32, [_P, C.POINTER(C.c_int32)]),
+    "gs_debug_device_scene_record": (C.c_int32, [_P, _P, C.c_int64]),
     "gs_device_scene_create": (C.c_int32, [_P, C.POINTER(_P)]),
     "gs_device_scene_destroy": (C.c_int32, [_P]),
     "gs_device_scene_info": (C.c_int32, [_P, C.POINTER(gs_scene_info)]),

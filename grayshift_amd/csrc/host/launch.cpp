@@ -1445,6 +1445,14 @@ gs_status gs_debug_last_launch_feat(const gs_device_scene* ds, int32_t* feat) {
     return GS_OK;
 }
 
+gs_status gs_debug_device_scene_record(const gs_device_scene* ds, void* out, int64_t out_bytes) {
+    if (!ds || !out) return fail(GS_ERR_ARG, "null argument");
+    if (out_bytes != (int64_t)sizeof(DevScene))
+        return fail(GS_ERR_ARG, "the device scene record is " + std::to_string(sizeof(DevScene)) + " bytes");
+    std::memcpy(out, &ds->dev, sizeof(DevScene));
+    return GS_OK;
+}
+
 gs_status gs_device_alloc(int64_t bytes, void** d_out) {
     if (!d_out || bytes < 0) return fail(GS_ERR_ARG, "bad argument");
     *d_out = nullptr;

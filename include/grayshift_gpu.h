@@ -311,6 +311,15 @@ gs_status gs_debug_set_guided_tail(int32_t fine_chunk, int32_t tail_pct);
  * Host only: read after the call that enqueued the launch returned. */
 gs_status gs_debug_last_launch_feat(const gs_device_scene* scene, int32_t* feat);
 
+/* Test hook: the scene's device record -- the struct of device pointers (the folded materials,
+ * the quads, textures, texels, the HDRI in the form chosen at upload, ...) and the background
+ * that every kernel launch of the scene passes by value -- copied into out.  Its layout is
+ * internal (csrc/device/kernel_abi.hpp, DevScene): for test kernels compiled from this tree,
+ * which run the product's device functions on the records the product built.  out_bytes must
+ * equal the record's size (GS_ERR_ARG else; the message states it).  The pointers stay valid
+ * until gs_device_scene_destroy.  Host only. */
+gs_status gs_debug_device_scene_record(const gs_device_scene* scene, void* out, int64_t out_bytes);
+
 /* Upload a flattened scene to the current HIP device. */
 gs_status gs_device_scene_create(const gs_flat_scene* scene, gs_device_scene** out);
 gs_status gs_device_scene_destroy(gs_device_scene* scene);

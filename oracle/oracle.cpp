@@ -1049,7 +1049,10 @@ static HittablePtr build_object(const gs_scene_spec& s, int idx, const std::vect
     }
 }
 
-static void build_world(const gs_scene_spec& s, World& w) {
+/* tops / tex_by_index (the batch entries below): the world's top-level objects kept apart
+ * instead of BVHNode::from_list(world), and every texture of the spec by its index. */
+static void build_world(const gs_scene_spec& s, World& w, std::vector<HittablePtr>* tops = nullptr,
+                        std::vector<const Texture*>* tex_by_index = nullptr) {
     std::vector<const Texture*> tmemo(s.n_textures > 0 ? s.n_textures : 0, nullptr);
     std::vector<const Material*> mats;
     for (int i = 0; i < s.n_materials; i++) {
@@ -1070,8 +1073,25 @@ static void build_world(const gs_scene_spec& s, World& w) {
     std::vector<HittablePtr> objs;
     for (int i = 0; i < s.n_world; i++) objs.push_back(build_object(s, s.world[i], mats));
     if (objs.empty()) throw std::runtime_error("empty world (reference panics)");
+    if (tex_by_index) {
+        for (int i = 0; i < s.n_textures; i++) build_texture(s, i, w, tmemo);
+        *tex_by_index = tmemo;
+    }
+    if (tops) {
+        *tops = std::move(objs);
+        return;
+    }
     w.root = BVHNode::construct_tree(std::move(objs));
 }
+
+/* A world for the batch entries (oracle_bounce, oracle_texture_value, oracle_background): its
+ * top-level objects one by one, its textures by index and its background. */
+struct BatchWorld {
+    World w;
+    std::vector<HittablePtr> tops;
+    std::vector<const Texture*> tex;
+    std::unique_ptr<Camera> cam;
+};
 
 static void add_counters(gs_counters& a, const gs_counters& b) {
     const uint64_t* pb = (const uint64_t*)&b;
@@ -1285,6 +1305,106 @@ int64_t oracle_bvh_topology(const gs_scene_spec* spec, int32_t* out, int64_t cap
         tl_err = ex.what();
         return -1;
     }
+}
+
+/* ---- batch entries over a world built once (tests/shade_cases.py): what Camera::ray_color
+ * calls after the world's hit, one case per element.  The spec (and the arrays it points to)
+ * must outlive the world. ---- */
+void* oracle_world_create(const gs_scene_spec* spec) {
+    try {
+        auto bw = std::make_unique<BatchWorld>();
+        build_world(*spec, bw->w, &bw->tops, &bw->tex);
+        gs_camera_spec c;
+        std::memset(&c, 0, sizeof(c));
+        c.aspect_ratio = 1.0; c.image_width = 1; c.max_depth = 1; c.v_fov = 90.0;
+        c.look_at[2] = -1.0; c.vup[1] = 1.0; c.focus_distance = 1.0;
+        gs_sample_settings ss = {0.95, 0.0, 1, 0};
+        bw->cam = std::make_unique<Camera>(c, ss, spec->background, 0);
+        return bw.release();
+    } catch (const std::exception& ex) {
+        tl_err = ex.what();
+        return nullptr;
+    }
+}
+void oracle_world_destroy(void* w) { delete (BatchWorld*)w; }
+int32_t oracle_world_tops(const void* w) { return (int32_t)((const BatchWorld*)w)->tops.size(); }
+
+/* One bounce on one object: case i takes top-level object k[i], ray (o, d, time) = ray[7 i ..]
+ * and stream state s0[i]; the object's own hit over Interval(0.001, f64::MAX), then on a hit
+ * emitted and scatter (camera.rs:179-195).
+ * out[18 i ..]: t, position, normal, u, v, emitted, attenuation, scattered direction;
+ * flags[4 i ..]: hit, front face, scatter's return, material index;
+ * state[2 i ..]: the stream after hit, after scatter; cnt[3 i ..]: image texels, noise
+ * evaluations, HDRI texels of the case.  Returns 0, or -1 for a bad object index. */
+int oracle_bounce(const void* world, int64_t n, const int32_t* k, const double* ray, const uint64_t* s0, double* out,
+                  int32_t* flags, uint64_t* state, uint64_t* cnt) {
+    const BatchWorld& bw = *(const BatchWorld*)world;
+    for (int64_t i = 0; i < n; i++) {
+        if (k[i] < 0 || k[i] >= (int32_t)bw.tops.size()) { tl_err = "object index out of range"; return -1; }
+        const double* r = ray + 7 * i;
+        Ray rr(Vec3(r[0], r[1], r[2]), Vec3(r[3], r[4], r[5]), r[6]);
+        std::memset(&tl_cnt, 0, sizeof(tl_cnt));
+        tl_rng.state = s0[i];
+        double* o = out + 18 * i;
+        for (int j = 0; j < 18; j++) o[j] = 0.0;
+        int32_t* f = flags + 4 * i;
+        f[0] = f[1] = f[2] = 0;
+        f[3] = -1;
+        HitRecord rec;
+        const bool hit = bw.tops[k[i]]->hit(rr, Interval(0.001, DBL_MAX), rec);
+        state[2 * i] = tl_rng.state;
+        if (hit) {
+            f[0] = 1;
+            f[1] = rec.is_front_face ? 1 : 0;
+            for (size_t m = 0; m < bw.w.materials.size(); m++)
+                if (bw.w.materials[m].get() == rec.material) f[3] = (int32_t)m;
+            o[0] = rec.t;
+            o[1] = rec.position.x; o[2] = rec.position.y; o[3] = rec.position.z;
+            o[4] = rec.normal.x; o[5] = rec.normal.y; o[6] = rec.normal.z;
+            o[7] = rec.u; o[8] = rec.v;
+            Vec3 e = rec.material->emitted(rec.u, rec.v, rec.position);
+            o[9] = e.x; o[10] = e.y; o[11] = e.z;
+            ScatterRecord s;
+            if (rec.material->scatter(rr, rec, s)) {
+                f[2] = 1;
+                o[12] = s.attenuation.x; o[13] = s.attenuation.y; o[14] = s.attenuation.z;
+                o[15] = s.scattered_ray.direction.x; o[16] = s.scattered_ray.direction.y;
+                o[17] = s.scattered_ray.direction.z;
+            }
+        }
+        state[2 * i + 1] = tl_rng.state;
+        cnt[3 * i] = tl_cnt.image_texels; cnt[3 * i + 1] = tl_cnt.noise_evals; cnt[3 * i + 2] = tl_cnt.hdri_texels;
+    }
+    return 0;
+}
+
+/* Texture::value_at(u, v, p) of texture tex[i]: uvp[5 i ..] = u, v, p; out[3 i ..] the colour;
+ * cnt[2 i ..]: image texels, noise evaluations. */
+int oracle_texture_value(const void* world, int64_t n, const int32_t* tex, const double* uvp, double* out,
+                         uint64_t* cnt) {
+    const BatchWorld& bw = *(const BatchWorld*)world;
+    for (int64_t i = 0; i < n; i++) {
+        if (tex[i] < 0 || tex[i] >= (int32_t)bw.tex.size()) { tl_err = "texture index out of range"; return -1; }
+        const double* a = uvp + 5 * i;
+        std::memset(&tl_cnt, 0, sizeof(tl_cnt));
+        Vec3 c = bw.tex[tex[i]]->value_at(a[0], a[1], Vec3(a[2], a[3], a[4]));
+        out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
+        cnt[2 * i] = tl_cnt.image_texels; cnt[2 * i + 1] = tl_cnt.noise_evals;
+    }
+    return 0;
+}
+
+/* Camera::sample_background of a ray along dir[3 i ..]: out[3 i ..] the colour, cnt[i] the HDRI
+ * texels read. */
+int oracle_background(const void* world, int64_t n, const double* dir, double* out, uint64_t* cnt) {
+    const BatchWorld& bw = *(const BatchWorld*)world;
+    for (int64_t i = 0; i < n; i++) {
+        std::memset(&tl_cnt, 0, sizeof(tl_cnt));
+        Vec3 c = bw.cam->sample_background(Ray(Vec3(), Vec3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]), 0.0));
+        out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
+        cnt[i] = tl_cnt.hdri_texels;
+    }
+    return 0;
 }
 
 } /* extern "C" */

@@ -56,8 +56,88 @@ def lib():
         L.oracle_checker_even.argtypes = [C.c_double, P]
         L.oracle_bvh_topology.restype = C.c_int64
         L.oracle_bvh_topology.argtypes = [C.POINTER(N.gs_scene_spec), P, C.c_int64]
+        L.oracle_world_create.restype = P
+        L.oracle_world_create.argtypes = [C.POINTER(N.gs_scene_spec)]
+        L.oracle_world_destroy.restype = None
+        L.oracle_world_destroy.argtypes = [P]
+        L.oracle_world_tops.restype = C.c_int32
+        L.oracle_world_tops.argtypes = [P]
+        L.oracle_bounce.argtypes = [P, C.c_int64, P, P, P, P, P, P, P]
+        L.oracle_texture_value.argtypes = [P, C.c_int64, P, P, P, P]
+        L.oracle_background.argtypes = [P, C.c_int64, P, P, P]
         _lib = L
     return _lib
+
+
+class World:
+    """A gs_scene_spec's world built once, for the batch entries: one bounce on one top-level
+    object, Texture::value_at and Camera::sample_background, n cases per call."""
+
+    def __init__(self, spec):
+        self._spec = spec  # (the world reads the spec's images and HDRI in place)
+        self._h = lib().oracle_world_create(spec.ptr())
+        if not self._h:
+            raise RuntimeError("oracle: " + lib().oracle_last_error().decode())
+        self.n_tops = lib().oracle_world_tops(self._h)
+
+    def close(self):
+        if self._h:
+            lib().oracle_world_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def bounce(self, k, ray, s0):
+        """k [n] top-level object, ray [n,7] (o, d, time), s0 [n] u64 stream state.  A dict of
+        arrays: hit, front, scatter (bool), mat (i32, -1 on a miss), t, p, n, u, v, emitted,
+        attenuation, dir, state_hit, state (u64: the stream after hit, after scatter), and the
+        counter deltas image_texels, noise_evals, hdri_texels."""
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        ray = np.ascontiguousarray(ray, dtype=np.float64)
+        s0 = np.ascontiguousarray(s0, dtype=np.uint64)
+        n = len(k)
+        assert ray.shape == (n, 7) and s0.shape == (n,)
+        out = np.zeros((n, 18))
+        flags = np.zeros((n, 4), dtype=np.int32)
+        state = np.zeros((n, 2), dtype=np.uint64)
+        cnt = np.zeros((n, 3), dtype=np.uint64)
+        if lib().oracle_bounce(self._h, n, k.ctypes.data, ray.ctypes.data, s0.ctypes.data, out.ctypes.data,
+                               flags.ctypes.data, state.ctypes.data, cnt.ctypes.data) != 0:
+            raise RuntimeError("oracle: " + lib().oracle_last_error().decode())
+        return {"hit": flags[:, 0] != 0, "front": flags[:, 1] != 0, "scatter": flags[:, 2] != 0,
+                "mat": flags[:, 3].copy(), "t": out[:, 0].copy(), "p": out[:, 1:4].copy(), "n": out[:, 4:7].copy(),
+                "u": out[:, 7].copy(), "v": out[:, 8].copy(), "emitted": out[:, 9:12].copy(),
+                "attenuation": out[:, 12:15].copy(), "dir": out[:, 15:18].copy(),
+                "state_hit": state[:, 0].copy(), "state": state[:, 1].copy(),
+                "image_texels": cnt[:, 0].copy(), "noise_evals": cnt[:, 1].copy(), "hdri_texels": cnt[:, 2].copy()}
+
+    def texture_value(self, tex, u, v, p):
+        """Texture::value_at(u, v, p) of spec texture tex[i]: (colour [n,3], image texels [n], noise evals [n])."""
+        tex = np.ascontiguousarray(tex, dtype=np.int32)
+        n = len(tex)
+        uvp = np.ascontiguousarray(np.column_stack([u, v, p]), dtype=np.float64)
+        assert uvp.shape == (n, 5)
+        out = np.zeros((n, 3))
+        cnt = np.zeros((n, 2), dtype=np.uint64)
+        if lib().oracle_texture_value(self._h, n, tex.ctypes.data, uvp.ctypes.data, out.ctypes.data,
+                                      cnt.ctypes.data) != 0:
+            raise RuntimeError("oracle: " + lib().oracle_last_error().decode())
+        return out, cnt[:, 0].copy(), cnt[:, 1].copy()
+
+    def background(self, d):
+        """Camera::sample_background(ray along d[i]): (colour [n,3], HDRI texels [n])."""
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        n = len(d)
+        assert d.shape == (n, 3)
+        out = np.zeros((n, 3))
+        cnt = np.zeros(n, dtype=np.uint64)
+        if lib().oracle_background(self._h, n, d.ctypes.data, out.ctypes.data, cnt.ctypes.data) != 0:
+            raise RuntimeError("oracle: " + lib().oracle_last_error().decode())
+        return out, cnt
 
 
 def _d(a):

@@ -14,6 +14,8 @@
 
 using namespace gsd;
 
+#include "../../grayshift_amd/csrc/device/shading.hpp"  // (after the using-directive: shading.hpp)
+
 __global__ void k_aabb(int n, const double* box, const double* ray, const double* iv, int* out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -111,7 +113,8 @@ __global__ void k_rng(int n, const uint64_t* seed, const uint32_t* pix, const ui
     for (int k = 0; k < draws; k++) out[(size_t)i * draws + k] = wy_f64(st);
 }
 
-// which: 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(x, y)
+// which: 0 sin, 1 cos, 2 acos, 3 asin, 4 atan2(x, y), 5 log (medium_test's free-flight draw),
+// 6 ldexp(1.0, (int)x - 136) (hdri_texel's RGBE scale for exponent byte x)
 __global__ void k_math(int n, int which, const double* x, const double* y, double* out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -128,6 +131,10 @@ __global__ void k_math(int n, int which, const double* x, const double* y, doubl
         r = acos(x[i]);
     } else if (which == 3) {
         r = asin(x[i]);
+    } else if (which == 5) {
+        r = log(x[i]);
+    } else if (which == 6) {
+        r = ldexp(1.0, (int)x[i] - 136);
     } else {
         r = atan2(x[i], y[i]);
     }
@@ -290,6 +297,100 @@ __global__ void k_udiv(int n, const uint32_t* num, const UDiv* u, uint32_t* out)
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     out[i] = udiv(num[i], u[i]);
+}
+
+// ---- the shading stage (shading.hpp) over the product's own device scene record, passed by
+// value as the render kernels' parameter block holds it.  One thread per case; cnt: C_N counters.
+__device__ __forceinline__ Ray ray_of(const double* r) {
+    Ray y;
+    y.o = mk(r[0], r[1], r[2]);
+    y.d = mk(r[3], r[4], r[5]);
+    y.time = r[6];
+    return y;
+}
+__device__ __forceinline__ void st3(double* o, d3 v) {
+    o[0] = v.x;
+    o[1] = v.y;
+    o[2] = v.z;
+}
+
+// which: 0 reconstruct<false>, 1 reconstruct<true>, 2 reconstruct_sphere<true>, 3
+// reconstruct_sphere<false>.  ray: o, d, time; refs: hit_ref, hit_inst, hit_outer.
+// out: p, n, u, v; mf: mat, front.
+__global__ void k_reconstruct(int n, int which, DevScene sc, const double* ray, const double* t, const uint32_t* refs,
+                              double* out, uint32_t* mf, unsigned long long* cnt) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Ray r = ray_of(ray + 7 * i);
+    const uint32_t ref = refs[3 * i], inst = refs[3 * i + 1], outer = refs[3 * i + 2];
+    HitRec h;
+    if (which == 0) h = reconstruct<false>(sc, r, t[i], ref, inst, outer);
+    else if (which == 1) h = reconstruct<true>(sc, r, t[i], ref, inst, outer);
+    else if (which == 2) h = reconstruct_sphere<true>(sc, r, t[i], ref);
+    else h = reconstruct_sphere<false>(sc, r, t[i], ref);
+    st3(out + 8 * i, h.p);
+    st3(out + 8 * i + 3, h.n);
+    out[8 * i + 6] = h.u;
+    out[8 * i + 7] = h.v;
+    mf[2 * i] = h.mat;
+    mf[2 * i + 1] = h.front ? 1u : 0u;
+}
+
+// which 0: texture_value(idx, u, v, p); 1: checker(mats[idx], p).  uvp: u, v, p.
+__global__ void k_texture(int n, int which, DevScene sc, const uint32_t* idx, const double* uvp, double* out,
+                          unsigned long long* cnt) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* a = uvp + 5 * i;
+    const d3 p = mk(a[2], a[3], a[4]);
+    st3(out + 3 * i, which == 0 ? texture_value(sc, idx[i], a[0], a[1], p, cnt) : checker(sc.mats[idx[i]], p));
+}
+
+// scatter() on a given HitRec (hr: p, n, u, v; mf: mat, front), in_dir and stream state.
+// out: col, dir; cont; the stream state after.
+__global__ void k_scatter(int n, DevScene sc, const double* hr, const uint32_t* mf, const double* in_dir,
+                          const uint64_t* rng, double* out, uint32_t* cont, uint64_t* rng_out, unsigned long long* cnt) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    HitRec h;
+    h.p = mk(hr[8 * i], hr[8 * i + 1], hr[8 * i + 2]);
+    h.n = mk(hr[8 * i + 3], hr[8 * i + 4], hr[8 * i + 5]);
+    h.u = hr[8 * i + 6];
+    h.v = hr[8 * i + 7];
+    h.mat = mf[2 * i];
+    h.front = mf[2 * i + 1] != 0;
+    const Scatter s = scatter(sc, h, mk(in_dir[3 * i], in_dir[3 * i + 1], in_dir[3 * i + 2]), rng[i], cnt);
+    st3(out + 6 * i, s.col);
+    st3(out + 6 * i + 3, s.dir);
+    cont[i] = s.cont;
+    rng_out[i] = s.rng;
+}
+
+// which: 0 shade<0,0,0>, 1 shade<0,0,1>, 2 shade<0,1,0>, 3 shade<1,1,0>.  A miss has hit_ref
+// GS_REF_NONE.  out: col, dir, the new ray.o; cont; the stream state after.
+__global__ void k_shade(int n, int which, DevScene sc, const double* ray, const double* t, const uint32_t* refs,
+                        const uint64_t* rng, double* out, uint32_t* cont, uint64_t* rng_out, unsigned long long* cnt) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray r = ray_of(ray + 7 * i);
+    const uint32_t ref = refs[3 * i], inst = refs[3 * i + 1], outer = refs[3 * i + 2];
+    uint64_t st = rng[i];
+    ShadeOut o;
+    if (which == 0) o = shade<false, false, false>(sc, r, t[i], ref, inst, st, cnt, outer);
+    else if (which == 1) o = shade<false, false, true>(sc, r, t[i], ref, inst, st, cnt, outer);
+    else if (which == 2) o = shade<false, true, false>(sc, r, t[i], ref, inst, st, cnt, outer);
+    else o = shade<true, true, false>(sc, r, t[i], ref, inst, st, cnt, outer);
+    st3(out + 9 * i, o.col);
+    st3(out + 9 * i + 3, o.dir);
+    st3(out + 9 * i + 6, r.o);
+    cont[i] = o.cont;
+    rng_out[i] = st;
+}
+
+__global__ void k_background(int n, DevScene sc, const double* dir, double* out, unsigned long long* cnt) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    st3(out + 3 * i, background(sc, mk(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]), cnt));
 }
 
 extern "C" {
@@ -477,6 +578,107 @@ int kat_udiv(int n, const uint32_t* num, const uint32_t* den, uint32_t* out) {
     back(out, dout, n);
     (void)hipFree(dn); (void)hipFree(du);
     return hipDeviceSynchronize() == hipSuccess ? 0 : -1;
+}
+
+// ---- the shading stage.  scene: the record gs_debug_device_scene_record copied out
+// (kat_dev_scene_bytes() bytes); cnt: C_N (kat_counters()) u64, the launch's counters.
+int kat_dev_scene_bytes(void) { return (int)sizeof(DevScene); }
+int kat_counters(void) { return (int)C_N; }
+// The slot of a counter the shading tests read: 0 hits, 1 image texels, 2 HDRI texels, 3 noise evaluations.
+int kat_counter_slot(int which) {
+    return which == 0 ? (int)C_HITS : which == 1 ? (int)C_IMG : which == 2 ? (int)C_HDRI : which == 3 ? (int)C_NOISE : -1;
+}
+int kat_dev_scene_rgbe(const void* scene) { return ((const DevScene*)scene)->hdri_rgbe != nullptr ? 1 : 0; }
+
+static unsigned long long* cnt_new() {
+    unsigned long long* d = dcopy<unsigned long long>(nullptr, C_N);
+    if (d) (void)hipMemset(d, 0, C_N * sizeof(unsigned long long));
+    return d;
+}
+static int finish(unsigned long long* cnt, unsigned long long* dcnt) {
+    const hipError_t e = hipDeviceSynchronize();
+    back(cnt, dcnt, C_N);
+    return e == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int kat_reconstruct(int n, int which, const void* scene, const double* ray, const double* t, const uint32_t* refs,
+                    double* out, uint32_t* mf, unsigned long long* cnt) {
+    const DevScene sc = *(const DevScene*)scene;
+    double *dr = dcopy(ray, 7 * (size_t)n), *dt = dcopy(t, n);
+    uint32_t* df = dcopy(refs, 3 * (size_t)n);
+    double* dout = dcopy<double>(nullptr, 8 * (size_t)n);
+    uint32_t* dmf = dcopy<uint32_t>(nullptr, 2 * (size_t)n);
+    unsigned long long* dcnt = cnt_new();
+    hipLaunchKernelGGL(k_reconstruct, grid(n), dim3(256), 0, 0, n, which, sc, dr, dt, df, dout, dmf, dcnt);
+    const int rc = finish(cnt, dcnt);
+    back(out, dout, 8 * (size_t)n);
+    back(mf, dmf, 2 * (size_t)n);
+    (void)hipFree(dr); (void)hipFree(dt); (void)hipFree(df);
+    return rc;
+}
+
+int kat_texture(int n, int which, const void* scene, const uint32_t* idx, const double* uvp, double* out,
+                unsigned long long* cnt) {
+    const DevScene sc = *(const DevScene*)scene;
+    uint32_t* di = dcopy(idx, n);
+    double* du = dcopy(uvp, 5 * (size_t)n);
+    double* dout = dcopy<double>(nullptr, 3 * (size_t)n);
+    unsigned long long* dcnt = cnt_new();
+    hipLaunchKernelGGL(k_texture, grid(n), dim3(256), 0, 0, n, which, sc, di, du, dout, dcnt);
+    const int rc = finish(cnt, dcnt);
+    back(out, dout, 3 * (size_t)n);
+    (void)hipFree(di); (void)hipFree(du);
+    return rc;
+}
+
+int kat_scatter(int n, const void* scene, const double* hr, const uint32_t* mf, const double* in_dir,
+                const uint64_t* rng, double* out, uint32_t* cont, uint64_t* rng_out, unsigned long long* cnt) {
+    const DevScene sc = *(const DevScene*)scene;
+    double *dh = dcopy(hr, 8 * (size_t)n), *dd = dcopy(in_dir, 3 * (size_t)n);
+    uint32_t* dmf = dcopy(mf, 2 * (size_t)n);
+    uint64_t* dg = dcopy(rng, n);
+    double* dout = dcopy<double>(nullptr, 6 * (size_t)n);
+    uint32_t* dc = dcopy<uint32_t>(nullptr, n);
+    uint64_t* dgo = dcopy<uint64_t>(nullptr, n);
+    unsigned long long* dcnt = cnt_new();
+    hipLaunchKernelGGL(k_scatter, grid(n), dim3(256), 0, 0, n, sc, dh, dmf, dd, dg, dout, dc, dgo, dcnt);
+    const int rc = finish(cnt, dcnt);
+    back(out, dout, 6 * (size_t)n);
+    back(cont, dc, n);
+    back(rng_out, dgo, n);
+    (void)hipFree(dh); (void)hipFree(dd); (void)hipFree(dmf); (void)hipFree(dg);
+    return rc;
+}
+
+int kat_shade(int n, int which, const void* scene, const double* ray, const double* t, const uint32_t* refs,
+              const uint64_t* rng, double* out, uint32_t* cont, uint64_t* rng_out, unsigned long long* cnt) {
+    const DevScene sc = *(const DevScene*)scene;
+    double *dr = dcopy(ray, 7 * (size_t)n), *dt = dcopy(t, n);
+    uint32_t* df = dcopy(refs, 3 * (size_t)n);
+    uint64_t* dg = dcopy(rng, n);
+    double* dout = dcopy<double>(nullptr, 9 * (size_t)n);
+    uint32_t* dc = dcopy<uint32_t>(nullptr, n);
+    uint64_t* dgo = dcopy<uint64_t>(nullptr, n);
+    unsigned long long* dcnt = cnt_new();
+    hipLaunchKernelGGL(k_shade, grid(n), dim3(256), 0, 0, n, which, sc, dr, dt, df, dg, dout, dc, dgo, dcnt);
+    const int rc = finish(cnt, dcnt);
+    back(out, dout, 9 * (size_t)n);
+    back(cont, dc, n);
+    back(rng_out, dgo, n);
+    (void)hipFree(dr); (void)hipFree(dt); (void)hipFree(df); (void)hipFree(dg);
+    return rc;
+}
+
+int kat_background(int n, const void* scene, const double* dir, double* out, unsigned long long* cnt) {
+    const DevScene sc = *(const DevScene*)scene;
+    double* dd = dcopy(dir, 3 * (size_t)n);
+    double* dout = dcopy<double>(nullptr, 3 * (size_t)n);
+    unsigned long long* dcnt = cnt_new();
+    hipLaunchKernelGGL(k_background, grid(n), dim3(256), 0, 0, n, sc, dd, dout, dcnt);
+    const int rc = finish(cnt, dcnt);
+    back(out, dout, 3 * (size_t)n);
+    (void)hipFree(dd);
+    return rc;
 }
 
 }  // extern "C"

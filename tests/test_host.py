@@ -64,7 +64,8 @@ def test_version_and_error_channel():
                                   "gs_background_spec", "gs_scene_spec", "gs_camera_spec", "gs_sample_settings",
                                   "gs_counters", "gs_camera", "gs_partition", "gs_background", "gs_flat_scene",
                                   "gs_render_outputs", "gs_launch", "gs_multi_outputs", "gs_stats",
-                                  "gs_scene_info"])
+                                  "gs_scene_info", "gs_node", "gs_sphere", "gs_msphere", "gs_quad", "gs_triangle",
+                                  "gs_instance", "gs_material", "gs_texture"])
 def test_struct_layouts_match(name):
     assert N.lib.gs_host_struct_size(name.encode()) == C.sizeof(getattr(N, name))
 
