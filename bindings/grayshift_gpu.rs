@@ -188,6 +188,12 @@ pub struct gs_scene_info {
     pub placement: i32, pub long_samples: i32, pub pilot_ms: f64,
 }
 
+/// What the leaf tests read beside the device record (test hook: gs_debug_leaf_stage_record).
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct gs_debug_leaf_stage {
+    pub tquads: *const c_void, pub n_quads: u32, pub n_cubes: u32, pub lds_quads: u32, pub lds_cubes: u32,
+}
+
 #[link(name = "grayshift")]
 extern "C" {
     pub fn gs_last_error() -> *const c_char;
@@ -206,6 +212,7 @@ extern "C" {
                                   stream: *mut c_void) -> gs_status;
     pub fn gs_debug_last_launch_feat(scene: *const gs_device_scene, feat: *mut i32) -> gs_status;
     pub fn gs_debug_device_scene_record(scene: *const gs_device_scene, out: *mut c_void, out_bytes: i64) -> gs_status;
+    pub fn gs_debug_leaf_stage_record(scene: *const gs_device_scene, out: *mut gs_debug_leaf_stage, out_bytes: i64) -> gs_status;
     pub fn gs_device_scene_create(scene: *const gs_flat_scene, out: *mut *mut gs_device_scene) -> gs_status;
     pub fn gs_device_scene_destroy(scene: *mut gs_device_scene) -> gs_status;
     pub fn gs_device_scene_info(scene: *const gs_device_scene, out: *mut gs_scene_info) -> gs_status;

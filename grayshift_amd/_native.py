@@ -258,6 +258,11 @@ class gs_views_adapt_info(C.Structure):
         return d
 
 
+class gs_debug_leaf_stage(C.Structure):
+    _fields_ = [("tquads", C.c_void_p), ("n_quads", C.c_uint32), ("n_cubes", C.c_uint32), ("lds_quads", C.c_uint32),
+                ("lds_cubes", C.c_uint32)]
+
+
 # Every symbol include/*.h declares, with its ctypes signature.
 _P = C.c_void_p
 SIGNATURES = {
@@ -277,6 +282,7 @@ SIGNATURES = {
                                            C.POINTER(gs_partition), _P, _P, _P]),
     "gs_debug_last_launch_feat": (C.c_int32, [_P, C.POINTER(C.c_int32)]),
     "gs_debug_device_scene_record": (C.c_int32, [_P, _P, C.c_int64]),
+    "gs_debug_leaf_stage_record": (C.c_int32, [_P, C.POINTER(gs_debug_leaf_stage), C.c_int64]),
     "gs_device_scene_create": (C.c_int32, [_P, C.POINTER(_P)]),
     "gs_device_scene_destroy": (C.c_int32, [_P]),
     "gs_device_scene_info": (C.c_int32, [_P, C.POINTER(gs_scene_info)]),

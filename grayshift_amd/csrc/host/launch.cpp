@@ -1453,6 +1453,14 @@ gs_status gs_debug_device_scene_record(const gs_device_scene* ds, void* out, int
     return GS_OK;
 }
 
+gs_status gs_debug_leaf_stage_record(const gs_device_scene* ds, gs_debug_leaf_stage* out, int64_t out_bytes) {
+    if (!ds || !out) return fail(GS_ERR_ARG, "null argument");
+    if (out_bytes != (int64_t)sizeof(gs_debug_leaf_stage))
+        return fail(GS_ERR_ARG, "the leaf stage record is " + std::to_string(sizeof(gs_debug_leaf_stage)) + " bytes");
+    *out = gs_debug_leaf_stage{ds->tquads, ds->n_quads, ds->n_cubes, ds->mirror.quads, ds->mirror.cubes};
+    return GS_OK;
+}
+
 gs_status gs_device_alloc(int64_t bytes, void** d_out) {
     if (!d_out || bytes < 0) return fail(GS_ERR_ARG, "bad argument");
     *d_out = nullptr;

@@ -320,6 +320,19 @@ gs_status gs_debug_last_launch_feat(const gs_device_scene* scene, int32_t* feat)
  * until gs_device_scene_destroy.  Host only. */
 gs_status gs_debug_device_scene_record(const gs_device_scene* scene, void* out, int64_t out_bytes);
 
+/* Test hook: what the leaf tests read beside the device record -- the device array of the quads'
+ * traversal records (n_quads records of 128 bytes, gs_quad order; layout internal: csrc/device/
+ * geometry.hpp, TQuad), the number of Quad::cube records (gs_debug_set_cube_lists) and the
+ * prefixes of both that the scene's current placement mirrors in LDS.  out_bytes must equal
+ * sizeof(gs_debug_leaf_stage) (GS_ERR_ARG else).  The pointer stays valid until
+ * gs_device_scene_destroy.  Host only; sets nothing. */
+typedef struct gs_debug_leaf_stage {
+    const void* tquads;
+    uint32_t n_quads, n_cubes;
+    uint32_t lds_quads, lds_cubes;
+} gs_debug_leaf_stage;
+gs_status gs_debug_leaf_stage_record(const gs_device_scene* scene, gs_debug_leaf_stage* out, int64_t out_bytes);
+
 /* Upload a flattened scene to the current HIP device. */
 gs_status gs_device_scene_create(const gs_flat_scene* scene, gs_device_scene** out);
 gs_status gs_device_scene_destroy(gs_device_scene* scene);

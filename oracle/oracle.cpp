@@ -1378,6 +1378,46 @@ int oracle_bounce(const void* world, int64_t n, const int32_t* k, const double* 
     return 0;
 }
 
+/* One object's own hit over a given interval: case i takes top-level object k[i], ray (o, d,
+ * time) = ray[7 i ..], Interval(iv[2 i], iv[2 i + 1]) and stream state s0[i] (a ConstantMedium
+ * draws from it inside hit, volume.rs:48).
+ * out[9 i ..]: t, position, normal, u, v; flags[3 i ..]: hit, front face, material index (-1 on a
+ * miss); state[i]: the stream after; cnt[8 i ..]: the case's node_visits, sphere_tests,
+ * msphere_tests, quad_tests, tri_tests, instance_tests, list_tests, medium_tests.
+ * Returns 0, or -1 for a bad object index. */
+int oracle_hit(const void* world, int64_t n, const int32_t* k, const double* ray, const double* iv, const uint64_t* s0,
+               double* out, int32_t* flags, uint64_t* state, uint64_t* cnt) {
+    const BatchWorld& bw = *(const BatchWorld*)world;
+    for (int64_t i = 0; i < n; i++) {
+        if (k[i] < 0 || k[i] >= (int32_t)bw.tops.size()) { tl_err = "object index out of range"; return -1; }
+        const double* r = ray + 7 * i;
+        Ray rr(Vec3(r[0], r[1], r[2]), Vec3(r[3], r[4], r[5]), r[6]);
+        std::memset(&tl_cnt, 0, sizeof(tl_cnt));
+        tl_rng.state = s0[i];
+        double* o = out + 9 * i;
+        for (int j = 0; j < 9; j++) o[j] = 0.0;
+        int32_t* f = flags + 3 * i;
+        f[0] = f[1] = 0;
+        f[2] = -1;
+        HitRecord rec;
+        if (bw.tops[k[i]]->hit(rr, Interval(iv[2 * i], iv[2 * i + 1]), rec)) {
+            f[0] = 1;
+            f[1] = rec.is_front_face ? 1 : 0;
+            for (size_t m = 0; m < bw.w.materials.size(); m++)
+                if (bw.w.materials[m].get() == rec.material) f[2] = (int32_t)m;
+            o[0] = rec.t;
+            o[1] = rec.position.x; o[2] = rec.position.y; o[3] = rec.position.z;
+            o[4] = rec.normal.x; o[5] = rec.normal.y; o[6] = rec.normal.z;
+            o[7] = rec.u; o[8] = rec.v;
+        }
+        state[i] = tl_rng.state;
+        uint64_t* c = cnt + 8 * i;
+        c[0] = tl_cnt.node_visits; c[1] = tl_cnt.sphere_tests; c[2] = tl_cnt.msphere_tests; c[3] = tl_cnt.quad_tests;
+        c[4] = tl_cnt.tri_tests; c[5] = tl_cnt.instance_tests; c[6] = tl_cnt.list_tests; c[7] = tl_cnt.medium_tests;
+    }
+    return 0;
+}
+
 /* Texture::value_at(u, v, p) of texture tex[i]: uvp[5 i ..] = u, v, p; out[3 i ..] the colour;
  * cnt[2 i ..]: image texels, noise evaluations. */
 int oracle_texture_value(const void* world, int64_t n, const int32_t* tex, const double* uvp, double* out,

@@ -63,6 +63,7 @@ def lib():
         L.oracle_world_tops.restype = C.c_int32
         L.oracle_world_tops.argtypes = [P]
         L.oracle_bounce.argtypes = [P, C.c_int64, P, P, P, P, P, P, P]
+        L.oracle_hit.argtypes = [P, C.c_int64, P, P, P, P, P, P, P, P]
         L.oracle_texture_value.argtypes = [P, C.c_int64, P, P, P, P]
         L.oracle_background.argtypes = [P, C.c_int64, P, P, P]
         _lib = L
@@ -114,6 +115,34 @@ class World:
                 "attenuation": out[:, 12:15].copy(), "dir": out[:, 15:18].copy(),
                 "state_hit": state[:, 0].copy(), "state": state[:, 1].copy(),
                 "image_texels": cnt[:, 0].copy(), "noise_evals": cnt[:, 1].copy(), "hdri_texels": cnt[:, 2].copy()}
+
+    HIT_COUNTERS = ("node_visits", "sphere_tests", "msphere_tests", "quad_tests", "tri_tests", "instance_tests",
+                    "list_tests", "medium_tests")
+
+    def hit(self, k, ray, tmin, tmax, s0):
+        """Top-level object k[i]'s own hit of ray[i] (o, d, time) over Interval(tmin[i], tmax[i]),
+        the stream at s0[i].  A dict of arrays: hit, front (bool), mat (i32, -1 on a miss), t, p, n,
+        u, v, state (u64: the stream after) and the case's test counters (HIT_COUNTERS, u64)."""
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        ray = np.ascontiguousarray(ray, dtype=np.float64)
+        s0 = np.ascontiguousarray(s0, dtype=np.uint64)
+        n = len(k)
+        iv = np.ascontiguousarray(np.column_stack([np.broadcast_to(tmin, (n,)), np.broadcast_to(tmax, (n,))]),
+                                  dtype=np.float64)
+        assert ray.shape == (n, 7) and s0.shape == (n,) and iv.shape == (n, 2)
+        out = np.zeros((n, 9))
+        flags = np.zeros((n, 3), dtype=np.int32)
+        state = np.zeros(n, dtype=np.uint64)
+        cnt = np.zeros((n, 8), dtype=np.uint64)
+        if lib().oracle_hit(self._h, n, k.ctypes.data, ray.ctypes.data, iv.ctypes.data, s0.ctypes.data, out.ctypes.data,
+                            flags.ctypes.data, state.ctypes.data, cnt.ctypes.data) != 0:
+            raise RuntimeError("oracle: " + lib().oracle_last_error().decode())
+        res = {"hit": flags[:, 0] != 0, "front": flags[:, 1] != 0, "mat": flags[:, 2].copy(), "t": out[:, 0].copy(),
+               "p": out[:, 1:4].copy(), "n": out[:, 4:7].copy(), "u": out[:, 7].copy(), "v": out[:, 8].copy(),
+               "state": state}
+        for j, name in enumerate(self.HIT_COUNTERS):
+            res[name] = cnt[:, j].copy()
+        return res
 
     def texture_value(self, tex, u, v, p):
         """Texture::value_at(u, v, p) of spec texture tex[i]: (colour [n,3], image texels [n], noise evals [n])."""

@@ -2,7 +2,9 @@
 // (grayshift_amd/csrc/device/geometry.hpp, devmath.hpp) over arrays of test cases so
 // tests/test_gpu_device_kat.py can compare them bit-for-bit with the CPU oracle on
 // adversarial inputs (zero / negative-zero direction components, origins on slab
-// planes, tangent rays, closed/open interval ends).  Not part of the product.
+// planes, tangent rays, closed/open interval ends), the shading stage (shading.hpp) for
+// tests/test_gpu_shading_kat.py and the leaf stage (leaf.hpp) for tests/test_gpu_leaf_kat.py.
+// Not part of the product.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,6 +16,7 @@
 
 using namespace gsd;
 
+#include "../../grayshift_amd/csrc/device/leaf.hpp"     // (after the using-directive, as render.hip)
 #include "../../grayshift_amd/csrc/device/shading.hpp"  // (after the using-directive: shading.hpp)
 
 __global__ void k_aabb(int n, const double* box, const double* ray, const double* iv, int* out) {
@@ -393,6 +396,100 @@ __global__ void k_background(int n, DevScene sc, const double* dir, double* out,
     st3(out + 3 * i, background(sc, mk(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]), cnt));
 }
 
+// ---- the leaf stage (leaf.hpp): leaf_other<FEAT, UNI> on the product's device scene, its quad
+// traversal records and cube records, one thread per case; a case whose ref is GS_REF_NONE is an
+// inactive lane (padding).  The block mirrors the first n_lds quad records and n_lcubes cube
+// records in dynamic LDS as gs_render_kernel does (quads first, then cubes, 16 B at a time).
+// flags (6 per case): hit, ref, inst, enter, HitRec mat, front.  out (21 per case): t, the ray as
+// leaf_other left it (o, d), the HitRec of reconstruct on a hit (p, n, u, v), and for enter != 0
+// the f64 box of the entered tree's root node.  cnt: C_N counters per case.  nonuni: set when a
+// UNI wave's active lanes did not share one ref.
+#define KAT_LEAF_FLAGS 6
+#define KAT_LEAF_OUT 21
+template <int FEAT, bool UNI>
+__device__ __forceinline__ void leaf_case(const DevScene& sc, const QuadSrc& qs, uint32_t ref, const double* ray,
+                                          const double* iv, uint64_t rng, uint32_t* flags, double* out,
+                                          uint64_t* rng_out, unsigned long long* cnt, uint32_t* nonuni) {
+    const Ray r0 = ray_of(ray);
+    Ray rl = r0;
+    LeafHit lh;
+    if (UNI) {  // the wave's ref by readfirstlane, as the leaf pass takes it
+        const uint32_t first = __builtin_amdgcn_readfirstlane(ref);
+        if (__builtin_amdgcn_ballot_w64(ref != first) != 0) atomicOr(nonuni, 1u);
+        lh = leaf_other<FEAT, true>(sc, qs, first, rl, iv[0], iv[1], rng, cnt);
+    } else {
+        lh = leaf_other<FEAT, false>(sc, qs, ref, rl, iv[0], iv[1], rng, cnt);
+    }
+    flags[0] = lh.hit ? 1u : 0u;
+    flags[1] = lh.ref;
+    flags[2] = lh.inst;
+    flags[3] = lh.enter;
+    flags[4] = 0xFFFFFFFFu;
+    flags[5] = 0u;
+    out[0] = lh.t;
+    st3(out + 1, rl.o);
+    st3(out + 4, rl.d);
+    for (int k = 7; k < KAT_LEAF_OUT; k++) out[k] = 0.0;
+    if (lh.hit) {
+        const HitRec h = reconstruct<(FEAT & GS_FEAT_GENERAL) != 0>(sc, r0, lh.t, lh.ref, lh.inst, GS_REF_NONE);
+        st3(out + 7, h.p);
+        st3(out + 10, h.n);
+        out[13] = h.u;
+        out[14] = h.v;
+        flags[4] = h.mat;
+        flags[5] = h.front ? 1u : 0u;
+    }
+    if ((FEAT & GS_FEAT_NESTED) && lh.enter != 0) {
+        const uint32_t link = sc.nroots[lh.enter - 1u];
+        if (link < THR_END) {
+            const DNode b = box64(sc.tboxes[link >> 5]);
+            out[15] = b.mnx; out[16] = b.mny; out[17] = b.mnz;
+            out[18] = b.mxx; out[19] = b.mxy; out[20] = b.mxz;
+        }
+    }
+    *rng_out = rng;
+}
+
+// which = 2 * f + uni; f: 0 no feature, 1 MEDIA, 2 NESTED, 3 MEDIA | NESTED, 4 MEDIA | NESTED | GENERAL
+__global__ void k_leaf(int n, int which, DevScene sc, const TQuad* tquads, uint32_t n_lds, uint32_t n_lcubes,
+                       const uint32_t* refs, const double* ray, const double* iv, const uint64_t* rng, uint32_t* flags,
+                       double* out, uint64_t* rng_out, unsigned long long* cnt, uint32_t* nonuni) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    uint8_t* s_quads = smem;
+    uint8_t* s_cubes = s_quads + (size_t)n_lds * sizeof(TQuad);
+    {
+        const uint4* src = reinterpret_cast<const uint4*>(tquads);
+        uint4* dst = reinterpret_cast<uint4*>(s_quads);
+        for (uint32_t k = threadIdx.x; k < n_lds * 8u; k += blockDim.x) dst[k] = src[k];
+        src = reinterpret_cast<const uint4*>(sc.cubes);
+        dst = reinterpret_cast<uint4*>(s_cubes);
+        for (uint32_t k = threadIdx.x; k < n_lcubes * (GS_CUBE_DOUBLES / 2); k += blockDim.x) dst[k] = src[k];
+    }
+    const QuadSrc qs{s_quads, tquads, n_lds, s_cubes, n_lcubes};
+    __syncthreads();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t ref = refs[i];
+    if (ref == GS_REF_NONE) return;
+#define KAT_LEAF(F, U) \
+    leaf_case<F, U>(sc, qs, ref, ray + 7 * i, iv + 2 * i, rng[i], flags + KAT_LEAF_FLAGS * i, out + KAT_LEAF_OUT * i, \
+                    rng_out + i, cnt + (size_t)C_N * i, nonuni)
+    switch (which) {
+        case 0: KAT_LEAF(0, false); break;
+        case 1: KAT_LEAF(0, true); break;
+        case 2: KAT_LEAF(GS_FEAT_MEDIA, false); break;
+        case 3: KAT_LEAF(GS_FEAT_MEDIA, true); break;
+        case 4: KAT_LEAF(GS_FEAT_NESTED, false); break;
+        case 5: KAT_LEAF(GS_FEAT_NESTED, true); break;
+        case 6: KAT_LEAF(GS_FEAT_MEDIA | GS_FEAT_NESTED, false); break;
+        case 7: KAT_LEAF(GS_FEAT_MEDIA | GS_FEAT_NESTED, true); break;
+        case 8: KAT_LEAF(GS_FEAT_MEDIA | GS_FEAT_NESTED | GS_FEAT_GENERAL, false); break;
+        case 9: KAT_LEAF(GS_FEAT_MEDIA | GS_FEAT_NESTED | GS_FEAT_GENERAL, true); break;
+        default: break;
+    }
+#undef KAT_LEAF
+}
+
 extern "C" {
 
 int kat_aabb(int n, const double* box, const double* ray, const double* iv, int* out) {
@@ -678,6 +775,60 @@ int kat_background(int n, const void* scene, const double* dir, double* out, uns
     const int rc = finish(cnt, dcnt);
     back(out, dout, 3 * (size_t)n);
     (void)hipFree(dd);
+    return rc;
+}
+
+// ---- the leaf stage.  tquads: the device array gs_debug_leaf_stage_record hands out (n_quads
+// records); n_cubes: the scene's cube records; n_lds <= n_quads and n_lcubes <= n_cubes: the
+// prefixes to mirror in LDS.  Outputs of inactive lanes (ref GS_REF_NONE) stay zero.  Returns 0,
+// -1 after a HIP error, -2 for arguments out of range (nothing is launched).
+int kat_leaf_flags(void) { return KAT_LEAF_FLAGS; }
+int kat_leaf_out(void) { return KAT_LEAF_OUT; }
+int kat_tquad_bytes(void) { return (int)sizeof(TQuad); }
+// The slot of a test counter, in oracle_hit's order: node visits, sphere, moving sphere, quad,
+// triangle, instance, list, medium tests.
+int kat_leaf_counter_slot(int which) {
+    const int slots[8] = {C_NODES, C_SPH, C_MSPH, C_QUAD, C_TRI, C_INST, C_LIST, C_MED};
+    return which >= 0 && which < 8 ? slots[which] : -1;
+}
+
+int kat_leaf(int n, int which, const void* scene, const void* tquads, uint32_t n_quads, uint32_t n_cubes,
+             uint32_t n_lds, uint32_t n_lcubes, const uint32_t* refs, const double* ray, const double* iv,
+             const uint64_t* rng, uint32_t* flags, double* out, uint64_t* rng_out, unsigned long long* cnt,
+             uint32_t* nonuni) {
+    const size_t lds = (size_t)n_lds * sizeof(TQuad) + (size_t)n_lcubes * (GS_CUBE_DOUBLES * 8);
+    if (n <= 0 || which < 0 || which > 9 || n_lds > n_quads || n_lcubes > n_cubes || lds > 48u * 1024u) return -2;
+    if ((n_quads != 0 && !tquads) || !scene) return -2;
+    const DevScene sc = *(const DevScene*)scene;
+    const size_t N = (size_t)n;
+    uint32_t* df = dcopy(refs, N);
+    double *dr = dcopy(ray, 7 * N), *di = dcopy(iv, 2 * N);
+    uint64_t* dg = dcopy(rng, N);
+    uint32_t* dflags = dcopy<uint32_t>(nullptr, KAT_LEAF_FLAGS * N);
+    double* dout = dcopy<double>(nullptr, KAT_LEAF_OUT * N);
+    uint64_t* dgo = dcopy<uint64_t>(nullptr, N);
+    unsigned long long* dcnt = dcopy<unsigned long long>(nullptr, C_N * N);
+    uint32_t* dnu = dcopy<uint32_t>(nullptr, 1);
+    if (!df || !dr || !di || !dg || !dflags || !dout || !dgo || !dcnt || !dnu) {
+        (void)hipFree(df); (void)hipFree(dr); (void)hipFree(di); (void)hipFree(dg); (void)hipFree(dflags);
+        (void)hipFree(dout); (void)hipFree(dgo); (void)hipFree(dcnt); (void)hipFree(dnu);
+        return -1;
+    }
+    (void)hipMemset(dflags, 0, KAT_LEAF_FLAGS * N * sizeof(uint32_t));
+    (void)hipMemset(dout, 0, KAT_LEAF_OUT * N * sizeof(double));
+    (void)hipMemset(dgo, 0, N * sizeof(uint64_t));
+    (void)hipMemset(dcnt, 0, C_N * N * sizeof(unsigned long long));
+    (void)hipMemset(dnu, 0, sizeof(uint32_t));
+    hipLaunchKernelGGL(k_leaf, grid(n), dim3(256), lds, 0, n, which, sc, (const TQuad*)tquads, n_lds, n_lcubes, df, dr,
+                       di, dg, dflags, dout, dgo, dcnt, dnu);
+    const hipError_t e = hipDeviceSynchronize();
+    const int rc = e == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -1;
+    back(flags, dflags, KAT_LEAF_FLAGS * N);
+    back(out, dout, KAT_LEAF_OUT * N);
+    back(rng_out, dgo, N);
+    back(cnt, dcnt, C_N * N);
+    back(nonuni, dnu, 1);
+    (void)hipFree(df); (void)hipFree(dr); (void)hipFree(di); (void)hipFree(dg);
     return rc;
 }
 

@@ -31,56 +31,127 @@ def _records(ptr, T):
     return C.cast(ptr, C.POINTER(T))
 
 
+class gs_list(C.Structure):
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32)]
+
+
+class Flat:
+    """The flat scene's records and (index) its top-level leaves by key = (media levels, anchor).
+    anchor: a primitive's first point (a sphere's centre, a quad's q, a triangle's a); a HittableList's
+    is its first member's, a BVH's the smallest of its leaves', a medium's its boundary's, one level
+    more.  It matches a leaf to its spec object; the material index cannot, alone: the flat scene
+    numbers materials as it meets them (a medium's boundary has one too), not as the spec does."""
+
+    def __init__(self, flat, index=True):
+        self.flat = flat
+        self.nodes, self.inst = _records(flat.nodes, N.gs_node), _records(flat.instances, N.gs_instance)
+        self.sph, self.msph = _records(flat.spheres, N.gs_sphere), _records(flat.mspheres, N.gs_msphere)
+        self.quads, self.tris = _records(flat.quads, N.gs_quad), _records(flat.triangles, N.gs_triangle)
+        self.media = _records(flat.media, N.gs_medium_rec)
+        self.lists, self.list_refs = _records(flat.lists, gs_list), _records(flat.list_refs, C.c_uint32)
+        self.leaves = {}
+        if index:
+            self._walk(flat.root)
+
+    def _walk(self, ref):
+        if ref == REF_NONE:
+            return
+        if (ref >> REF_SHIFT) == REF_NODE:
+            n = self.nodes[ref & REF_MASK]
+            self._walk(n.left)
+            self._walk(n.right)
+            return
+        key = self.key(ref)
+        assert key not in self.leaves, "two leaves share the key %r" % (key,)
+        self.leaves[key] = ref
+
+    def chain(self, ref):
+        """The instance records of a chain, outermost first, and the ref it ends in."""
+        recs = []
+        while (ref >> REF_SHIFT) == REF_INST:
+            recs.append(self.inst[ref & REF_MASK])
+            ref = recs[-1].child
+        return recs, ref
+
+    def members(self, ref):
+        l = self.lists[ref & REF_MASK]
+        return [self.list_refs[l.first + j] for j in range(l.count)]
+
+    def tree_leaves(self, ref):
+        if (ref >> REF_SHIFT) != REF_NODE:
+            return [ref]
+        n = self.nodes[ref & REF_MASK]
+        return self.tree_leaves(n.left) + (self.tree_leaves(n.right) if n.right != REF_NONE else [])
+
+    def key(self, ref):
+        _, end = self.chain(ref)
+        kind, i = end >> REF_SHIFT, end & REF_MASK
+        if kind == REF_SPHERE:
+            return 0, tuple(self.sph[i].center)
+        if kind == REF_MSPHERE:
+            return 0, tuple(self.msph[i].center_start)
+        if kind == REF_QUAD:
+            return 0, tuple(self.quads[i].q)
+        if kind == REF_TRI:
+            return 0, tuple(self.tris[i].a)
+        if kind == REF_LIST:
+            return self.key(self.members(end)[0])
+        if kind == REF_NODE:
+            return 0, min(self.key(x)[1] for x in self.tree_leaves(end))
+        if kind == REF_MEDIUM:
+            lv, a = self.key(self.media[i].boundary)
+            return lv + 1, a
+        raise ValueError("leaf kind %d is not part of these scenes" % kind)
+
+    def materials(self, ref):
+        """The flat materials a hit of this leaf can carry, in member order."""
+        _, end = self.chain(ref)
+        kind, i = end >> REF_SHIFT, end & REF_MASK
+        if kind == REF_LIST:
+            return [m for x in self.members(end) for m in self.materials(x)]
+        if kind == REF_NODE:
+            return []
+        return [{REF_SPHERE: self.sph, REF_MSPHERE: self.msph, REF_QUAD: self.quads, REF_TRI: self.tris,
+                 REF_MEDIUM: self.media}[kind][i].material]
+
+    def forward(self, ref, o, d):
+        """A ray through the leaf's chain as Translate::hit / RotateY::hit transform it
+        (hittable.rs:107-113, 179-193), in their operations' order; o, d: [n, 3].  (o, d, end ref)."""
+        recs, end = self.chain(ref)
+        o, d = np.array(o, dtype=np.float64), np.array(d, dtype=np.float64)
+        for rec in recs:
+            if rec.kind == 1:  # GS_INST_TRANSLATE
+                o = o - np.array(rec.p[:])
+            else:
+                s, c = rec.p[0], rec.p[1]
+                o = np.stack([(c * o[:, 0]) - (s * o[:, 2]), o[:, 1], (s * o[:, 0]) + (c * o[:, 2])], -1)
+                d = np.stack([(c * d[:, 0]) - (s * d[:, 2]), d[:, 1], (s * d[:, 0]) + (c * d[:, 2])], -1)
+        return o, d, end
+
+
 def flat_leaves(flat):
     """The flat tree's leaves as {anchor: (hit_ref, hit_inst, hit_outer, material)}: the
     primitive (or medium) at the end of the leaf's chain and the refs a hit on it carries --
     its own chain, and for a chain inside a BVH under a chain that BVH's chain too (a plain
-    member of such a BVH carries the BVH's chain as its own).  anchor: the primitive's first
-    point (a sphere's centre, a quad's q, a triangle's a; a medium: its boundary's).  It matches a
-    leaf to its spec object; the material index cannot, alone: the flat scene numbers materials as
-    it meets them (a medium's boundary has one too), not as the spec does."""
-    nodes, inst = _records(flat.nodes, N.gs_node), _records(flat.instances, N.gs_instance)
-    sph, msph = _records(flat.spheres, N.gs_sphere), _records(flat.mspheres, N.gs_msphere)
-    quads, tris = _records(flat.quads, N.gs_quad), _records(flat.triangles, N.gs_triangle)
-    media = _records(flat.media, N.gs_medium_rec)
+    member of such a BVH carries the BVH's chain as its own).  anchor: Flat's."""
+    F = Flat(flat, index=False)
     out = {}
-
-    def chain_end(ref):
-        n = 0
-        while (ref >> REF_SHIFT) == REF_INST:
-            ref = inst[ref & REF_MASK].child
-            n += 1
-        return ref, n
-
-    def anchor_mat(ref):
-        kind, i = ref >> REF_SHIFT, ref & REF_MASK
-        if kind == REF_SPHERE:
-            return tuple(sph[i].center), sph[i].material
-        if kind == REF_MSPHERE:
-            return tuple(msph[i].center_start), msph[i].material
-        if kind == REF_QUAD:
-            return tuple(quads[i].q), quads[i].material
-        if kind == REF_TRI:
-            return tuple(tris[i].a), tris[i].material
-        if kind == REF_MEDIUM:
-            return anchor_mat(chain_end(media[i].boundary)[0])[0], media[i].material
-        raise ValueError("leaf kind %d is not part of these scenes" % kind)
 
     def walk(ref, outer):
         if ref == REF_NONE:
             return
         if (ref >> REF_SHIFT) == REF_NODE:
-            n = nodes[ref & REF_MASK]
+            n = F.nodes[ref & REF_MASK]
             walk(n.left, outer)
             walk(n.right, outer)
             return
-        end, _ = chain_end(ref)
+        _, end = F.chain(ref)
         chain = ref if (ref >> REF_SHIFT) == REF_INST else REF_NONE
         if (end >> REF_SHIFT) == REF_NODE:
             assert outer == REF_NONE
             walk(end, ref)
             return
-        a, m = anchor_mat(end)
+        a, m = F.key(end)[1], F.materials(end)[0]
         assert a not in out, "two leaves share an anchor"
         if outer != REF_NONE and chain != REF_NONE:
             out[a] = (end, chain, outer, m)

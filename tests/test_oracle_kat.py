@@ -295,3 +295,62 @@ def test_noise_texture_value_formula():
     for scale, z in [(4.0, 3.0), (0.2, -8.0)]:
         p = np.array([5.0, -2.0, z])
         assert oracle.noise_value(scale, p) == 0.5 * (1.0 + math.sin(scale * z))
+
+
+# ------------------------------------------------- oracle_hit: one object's hit over an interval
+def _hit_world():
+    """0: the unit quad q = (0, 0, 2), u = (1, 0, 0), v = (0, 1, 0); 1: the sphere of radius 1 at
+    (0, 0, 5); 2: the triangle (0, 0, -2), (0, 1, -2), (1, 0, -2), whose normal (b - a) x (c - a)
+    points along -z, so a ray along +z meets it from the culling test's accepted side."""
+    import grayshift_amd as g
+    b = g.SceneBuilder()
+    m = [b.lambertian((0.5, 0.5, 0.5)), b.metal((0.5, 0.5, 0.5), 0.0), b.dielectric(1.5)]
+    b.add(b.quad((0.0, 0.0, 2.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), m[0]))
+    b.add(b.sphere((0.0, 0.0, 5.0), 1.0, m[1]))
+    b.add(b.triangle((0.0, 0.0, -2.0), (0.0, 1.0, -2.0), (1.0, 0.0, -2.0), m[2]))
+    b.background_solid((0.0, 0.0, 0.0))
+    spec = b.build()
+    return oracle.World(spec), m
+
+
+def test_hit_quad_at_exactly_tmin_is_accepted():
+    # plane.rs:20-32: t = (D - n.o) / n.d = (2 - 0) / 1 = 2; Interval::contains is closed, so
+    # tmin = 2 accepts (and so does tmax = 2); alpha = 0.25, beta = 0.5 (quad.rs:90-95)
+    w, m = _hit_world()
+    ray = np.array([[0.25, 0.5, 0.0, 0.0, 0.0, 1.0, 0.0]] * 3)
+    a = w.hit([0, 0, 0], ray, [2.0, 0.001, np.nextafter(2.0, 3.0)], [1e300, 2.0, 1e300],
+              np.array([7, 7, 7], dtype=np.uint64))
+    assert list(a["hit"]) == [True, True, False]
+    assert list(a["t"][:2]) == [2.0, 2.0] and list(a["u"][:2]) == [0.25, 0.25] and list(a["v"][:2]) == [0.5, 0.5]
+    assert a["mat"][0] == m[0] and not a["front"][0] and tuple(a["n"][0]) == (0.0, 0.0, -1.0)
+    assert tuple(a["p"][0]) == (0.25, 0.5, 2.0)
+    assert list(a["quad_tests"]) == [1, 1, 1] and list(a["state"]) == [7, 7, 7]
+    assert a["sphere_tests"].sum() == 0 and a["node_visits"].sum() == 0
+
+
+def test_hit_sphere_root_at_exactly_tmin_is_rejected():
+    # sphere.rs:64-106: oc = (0, 0, 5), a = 1, h = 5, c = 24, disc = 1: roots 4 and 6, tested with
+    # Interval::surrounds (open).  tmin = 4 rejects the near root and takes 6; (4, 6) rejects both.
+    w, m = _hit_world()
+    ray = np.array([[0.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0]] * 3)
+    a = w.hit([1, 1, 1], ray, [4.0, 4.0, np.nextafter(4.0, 0.0)], [1e300, 6.0, 1e300], np.zeros(3, dtype=np.uint64))
+    assert list(a["hit"]) == [True, False, True]
+    assert a["t"][0] == 6.0 and not a["front"][0] and a["t"][2] == 4.0 and a["front"][2]
+    assert a["mat"][0] == m[1] and a["mat"][1] == -1
+    assert list(a["sphere_tests"]) == [1, 1, 1]
+
+
+def test_hit_triangle_behind_the_origin_is_accepted():
+    # triangle.rs:34-68 never reads ray_t: e1 = c - a = (1, 0, 0), e2 = b - a = (0, 1, 0), p = d x e2 =
+    # (-1, 0, 0) for d = (0, 0, 1), det = e1.p = -1 < EPS: culled.  With d = (0, 0, -1): p = (1, 0, 0),
+    # det = 1; t_vec = o - a = (0.25, 0.25, 2), u = 0.25; q = t_vec x e1 = (0, 2, -0.25), v = d.q = 0.25,
+    # t = e2.q = 2: the triangle lies at t = +2 along -z.  From o' = (0.25, 0.25, -4): t_vec.z = -2,
+    # q = (0, -2, -0.25), t = -2: behind the origin, and accepted over (0.001, 1).
+    w, m = _hit_world()
+    ray = np.array([[0.25, 0.25, 0.0, 0.0, 0.0, 1.0, 0.0], [0.25, 0.25, 0.0, 0.0, 0.0, -1.0, 0.0],
+                    [0.25, 0.25, -4.0, 0.0, 0.0, -1.0, 0.0]])
+    a = w.hit([2, 2, 2], ray, 0.001, [1e300, 1.0, 1.0], np.zeros(3, dtype=np.uint64))
+    assert list(a["hit"]) == [False, True, True]
+    assert a["t"][1] == 2.0 and a["t"][2] == -2.0
+    assert a["u"][2] == 0.25 and a["v"][2] == 0.25 and a["mat"][2] == m[2]
+    assert tuple(a["p"][2]) == (0.25, 0.25, -2.0) and list(a["tri_tests"]) == [1, 1, 1]
