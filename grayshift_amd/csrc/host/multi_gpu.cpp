@@ -15,6 +15,13 @@
 // RCCL is resolved at run time (dlopen), so single-GPU users never load it, and the copy
 // that matches the process's HIP runtime is used (torch bundles both: one HIP runtime
 // per process).
+//
+// Layout: a context holds at most one open session (Session), whose record (AccumState,
+// ViewsAccumState, AdaptState) and per-device buffers (AccumBufs, AdaptBufs) live from its begin to
+// close_session; gs_multi::admit alone decides which call may run under which session.
+// gs_multi::render draws a Frame (a one-shot frame or a pass of the open session) in stages, one
+// function each; the sessions differ in three spots (launch_rank, read_back_session, note_pass).
+// The tile partition is cached by camera, kind and tile height: a views session cuts at its own.
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
@@ -110,9 +117,7 @@ struct DBuf {
     size_t bytes = 0;
     bool ensure(size_t need) {
         if (bytes >= need && p) return true;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
+        release();
         if (hipMalloc(&p, need + 16) != hipSuccess) return false;
         bytes = need;
         return true;
@@ -124,6 +129,33 @@ struct DBuf {
     }
 };
 
+// One device's buffers of an open accumulation, plain or of views: the rank's running sums (cap * 3
+// f64, packed order) and the last pass's change partials, with their pinned host copy.
+struct AccumBufs {
+    DBuf sums, delta;
+    double* h_delta = nullptr;
+    void release() {
+        for (DBuf* b : {&sums, &delta}) b->release();
+        if (h_delta) (void)hipHostFree(h_delta);
+        h_delta = nullptr;
+    }
+};
+
+// One device's buffers of an open adaptation, plain or of views: the rank's round state (launch.cpp's
+// blob), the two maps in packed order (cap u32, cap f32), the pinned copy of the blob's summary
+// words, and the rank's paths so far in the adaptation's device counters.  The summary's 24 pinned
+// bytes stay from the first adaptation to the context's end (pinning them anew costs every adaptation).
+struct AdaptBufs {
+    DBuf rstate, map_samples, map_error;
+    unsigned long long* h_summary = nullptr;
+    uint64_t paths = 0;
+    void release(bool context_ends = false) {
+        for (DBuf* b : {&rstate, &map_samples, &map_error}) b->release();
+        if (h_summary && context_ends) (void)hipHostFree(h_summary), h_summary = nullptr;
+        paths = 0;
+    }
+};
+
 struct Device {
     int id = 0;
     gs_device_scene* scene = nullptr;
@@ -131,15 +163,8 @@ struct Device {
     // render start / end, megakernel start / end, gather + unpack start / end
     hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     DBuf order, packed, packed8, cnt;
-    // an open accumulation (gs_multi_accum_*): the rank's running sums (cap * 3 f64, packed
-    // order) and the last pass's per-block change, with its pinned host copy
-    DBuf sums, delta;
-    double* h_delta = nullptr;
-    // an open adaptation (gs_multi_adapt_*): the rank's round state (launch.cpp's blob), the two
-    // maps in packed order (cap u32, cap f32) and the pinned copy of the blob's summary words
-    DBuf rstate, map_samples, map_error;
-    unsigned long long* h_summary = nullptr;
-    uint64_t ad_paths = 0;  // this rank's paths so far in the adaptation's device counters
+    AccumBufs acc;  // (only one of the two is in use: the open session's)
+    AdaptBufs ad;
     // the frame's counters, copied back on the stream behind the frame's last work, so the
     // host's wait is the only synchronisation (a synchronous copy after it cost C1 ~25 us)
     gs_counters* h_cnt = nullptr;  // pinned
@@ -177,6 +202,76 @@ gs_status adapt_settings_check(const gs_sample_settings* ss) {
 int g_collective_always = 0;  // gs_debug_set_multi_collective
 int g_same_device = 0;        // gs_debug_set_multi_same_device
 
+// At most one session is open on a context (gs_multi_*_begin .. _end): its camera(s), seed(s) and
+// settings are fixed, and so is the tile partition computed at its begin, in whose packed order
+// the ranks' session buffers are.  What a call needs of it (gs_multi::admit): Begin opens session
+// s, so none may be open; Frame renders a frame of s (None: a one-shot frame), Pass and Other are
+// s's own calls, so s must be the open one.
+enum class Session { None, Accum, ViewsAccum, Adapt, ViewsAdapt };
+enum class Call { Begin, Frame, Pass, Other };
+
+// An open accumulation: `samples` samples of every pixel are in the ranks' sums.
+struct AccumState {
+    gs_camera cam{};
+    uint64_t seed = 0, samples = 0;
+    uint32_t chunk = 0, passes = 0;
+    double last_delta = 0.0;
+    gs_counters counters{};
+};
+
+// An open views accumulation: the tall frame is cut round-robin into tw x th tiles (gs_views_tile_h: no
+// tile straddles two views), view v's sums hold samples[v] samples, the change partials are one a tile slot.
+struct ViewsAccumState {
+    std::vector<gs_view> views;
+    gs_camera tall{};
+    int32_t th = 0;
+    uint32_t chunk = 0, passes = 0;
+    std::vector<uint32_t> samples;
+    std::vector<double> delta;
+    gs_counters counters{};
+};
+
+// An open adaptation: `rounds` rounds are in the ranks' state.  With `views` a views adaptation: cam
+// is then the tall frame's, cut round-robin into tw x th tiles like a views accumulation.
+struct AdaptState {
+    gs_camera cam{};
+    gs_sample_settings ss{};
+    int32_t th = 0;
+    uint64_t seed = 0, active = 0, samples_total = 0, samples_max = 0;
+    uint32_t rounds = 0, R = 0;
+    // The ranks' device counters run on from pass to pass (gs_round_params_kernel sizes a round's
+    // items by the rays per path so far, as in a one-shot launch): zeroed by the first pass after
+    // _begin / _upload (fresh), their sum so far in `dev`, and counters = base (an upload's) + dev.
+    bool fresh = true;
+    gs_counters counters{}, base{}, dev{};
+    std::vector<gs_view> views;
+    bool finished() const { return rounds > 0 && (active == 0 || rounds >= R); }
+};
+
+// What one render() draws: a one-shot frame (session None) or a pass of the open session.  (Any frame
+// has the first five, given in this order; the rest are set by name.)
+struct Frame {
+    Session session = Session::None;
+    const gs_camera* cam = nullptr;  // (a views frame: the tall frame's camera)
+    const gs_sample_settings* ss = nullptr;  // (an accumulation's pass: batch_size is its samples)
+    uint64_t seed = 0;               // (a views frame: unused, the views have their own)
+    int32_t th = 0;                  // the tile height of its partition
+    const gs_view* views = nullptr;  // a views frame: cut round-robin whatever `plan` says
+    uint32_t n_views = 0, chunk = 0, rounds = 0;  // (rounds: an adaptation's pass; 0 resolves the state as it stands)
+    const uint8_t* selected = nullptr;  // a views accumulation's pass: over these views (NULL: all),
+    uint32_t base = 0;                  // which all hold `base` samples
+};
+
+// One render() in flight: what its stages hand on.
+struct Shot {
+    const Frame& f;
+    const gs_multi_outputs* out;
+    bool want_rgb, want8, direct, timed_tail;
+    int64_t W, H;
+    const void *src = nullptr, *src8 = nullptr;  // what the unpack reads: packed or gathered tiles
+    gs_stats st{};  // (its counters: the ranks' sum, made the pass's own by note_pass)
+};
+
 }  // namespace
 
 struct gs_multi {
@@ -187,12 +282,13 @@ struct gs_multi {
     // gather done by device copies on the ranks' streams instead of RCCL (N > 1, no comms)
     bool copy_gather = false;
     bool comms_broken = false;      // a collective failed: the communicators were aborted
-    int32_t tw = 64, th = 64;
+    int32_t tw = 64, th = 64;       // (th: a views session cuts its frame at its own)
     bool plan = false;
     mutable std::mutex mu;  // one frame at a time; guards every field below and comms_broken
-    // tile partition of the last camera (plan or round-robin)
-    bool part_ready = false, part_rr = false;  // (part_rr: cut round-robin for a views call)
+    // tile partition of the last frame (plan or round-robin), kept while camera, kind and tile height are
+    bool part_ready = false, part_rr = false;  // (part_rr: cut round-robin for a views frame)
     gs_camera part_cam{};
+    int32_t part_th = 0;
     std::vector<int32_t> order;  // empty: round-robin
     int32_t slots = 0;
     int64_t cap = 0;  // packed pixels per rank
@@ -200,46 +296,11 @@ struct gs_multi {
     DBuf gathered, gathered8, frame, frame8, text, scratch, len;
     bool have_rgb = false, have_rgb8 = false;
     int32_t frame_w = 0, frame_h = 0;
-    // The open accumulation (gs_multi_accum_begin .. _end): camera, seed and chunk are fixed,
-    // the tile plan is the one computed at its start, and acc_samples samples of every pixel
-    // are in the ranks' sums.
-    bool acc_open = false;
-    gs_camera acc_cam{};
-    uint64_t acc_seed = 0, acc_samples = 0;
-    uint32_t acc_chunk = 0, acc_passes = 0;
-    double acc_last_delta = 0.0;
-    gs_counters acc_counters{};
-    // The open adaptation (gs_multi_adapt_begin .. _end): camera, settings and seed are fixed, the
-    // tile plan is the one computed at its start, and ad_rounds rounds are in the ranks' state.
-    bool ad_open = false;
-    gs_camera ad_cam{};
-    gs_sample_settings ad_ss{};
-    uint64_t ad_seed = 0, ad_active = 0, ad_samples_total = 0, ad_samples_max = 0;
-    uint32_t ad_rounds = 0, ad_R = 0;
-    // The ranks' device counters run on from pass to pass (gs_round_params_kernel sizes a round's
-    // items by the rays per path so far, as in a one-shot launch): zeroed by the first pass after
-    // _begin / _upload (ad_fresh), their sum over the ranks so far in ad_dev, and ad_counters =
-    // ad_base (an upload's) + ad_dev.
-    bool ad_fresh = true;
-    gs_counters ad_counters{}, ad_base{}, ad_dev{};
-    // The open views accumulation (gs_multi_views_accum_begin .. _end): the views and the chunk are
-    // fixed, the tall frame is cut round-robin into tw x va_th tiles (`th` holds va_th while it is
-    // open, th_ctx the context's own), view v's sums hold va_samples[v] samples.  The ranks' sums
-    // and change partials are the accumulation's buffers (Device::sums, delta: one per tile slot),
-    // acc_cam the tall frame's camera (permute_sums).
-    bool va_open = false;
-    int32_t th_ctx = 64;
-    std::vector<gs_view> va_views;
-    gs_camera va_tall{};
-    uint32_t va_chunk = 0, va_passes = 0;
-    std::vector<uint32_t> va_samples;
-    std::vector<double> va_delta;
-    gs_counters va_counters{};
-    // The open views adaptation (gs_multi_views_adapt_begin .. _end): an adaptation (ad_open and
-    // every ad_* field above) whose camera is the tall frame's, cut round-robin into tw x
-    // gs_views_tile_h tiles like a views accumulation (`th`, th_ctx), with the views' records.
-    bool vd_open = false;
-    std::vector<gs_view> vd_views;
+    // the open session and its record (the other records are empty)
+    Session open = Session::None;
+    AccumState acc;
+    ViewsAccumState va;
+    AdaptState ad;
 
     ~gs_multi() {
         DeviceGuard g;
@@ -255,17 +316,9 @@ struct gs_multi {
             (void)hipSetDevice(d.id);
             for (auto e : d.ev)
                 if (e) (void)hipEventDestroy(e);
-            d.order.release();
-            d.packed.release();
-            d.packed8.release();
-            d.cnt.release();
-            d.sums.release();
-            d.delta.release();
-            d.rstate.release();
-            d.map_samples.release();
-            d.map_error.release();
-            if (d.h_delta) (void)hipHostFree(d.h_delta);
-            if (d.h_summary) (void)hipHostFree(d.h_summary);
+            for (DBuf* b : {&d.order, &d.packed, &d.packed8, &d.cnt}) b->release();
+            d.acc.release();
+            d.ad.release(true);
             if (d.h_cnt) (void)hipHostFree(d.h_cnt);
             if (d.scene) gs_device_scene_destroy(d.scene);
             if (d.stream) (void)hipStreamDestroy(d.stream);
@@ -287,63 +340,105 @@ struct gs_multi {
         return fail(GS_ERR_HIP, what);
     }
 
-    // round_robin: no cost plan whatever `plan` says (a views call's tall frame)
-    gs_status partition(const gs_camera* cam, uint64_t seed, double* plan_ms, bool round_robin = false);
-    // pass_samples != 0: a pass of the open accumulation (cam, ss and seed are then its own)
-    // adapt: a pass of the open adaptation, of adapt_rounds rounds (0: resolve the state as it stands)
-    // vw: a views call (cam is then the tall frame's camera, ss one batch of its samples; the
-    // views' own seeds)
-    struct ViewsCall {
-        const gs_view* views;
-        uint32_t n, chunk;
-    };
-    // vp: a pass of the open views accumulation (with vw: its views), over the views `selected`
-    // (NULL: all), which all hold `base` samples
-    struct ViewsPass {
-        const uint8_t* selected;
-        uint32_t base;
-    };
-    gs_status render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, const gs_multi_outputs* out,
-                     gs_stats* stats, uint32_t pass_samples = 0, bool adapt = false, uint32_t adapt_rounds = 0,
-                     const ViewsCall* vw = nullptr, const ViewsPass* vp = nullptr);
-    gs_status views_accum_begin(const gs_view* views, uint32_t n_views, uint32_t chunk);
-    void views_accum_end();
+    gs_status admit(Call call, Session s) const;
+    // Ends the open session or undoes a failed begin: waits, frees its buffers, empties the records.
+    void close_session();
+    // round_robin: no cost plan whatever `plan` says (a views frame); plan_ms (nullable): a new cut's cost
+    gs_status partition(const gs_camera* cam, uint64_t seed, double* plan_ms, bool round_robin, int32_t tile_h);
+    // A frame, and its stages in their order (prepare: partition, placement pilots, buffers; gather: RCCL,
+    // device copies or none; unpack: PPM text and the queued read-backs too; wait: then counters and outputs).
+    gs_status render(const Frame& f, const gs_multi_outputs* out, gs_stats* stats);
+    gs_status check_frame(const Frame& f, const gs_multi_outputs* out) const;
+    gs_status prepare(Shot& c);
+    gs_status launch(Shot& c);
+    gs_status gather(Shot& c);
+    gs_status unpack(Shot& c);
+    gs_status wait(Shot& c);
+    // ... and the three spots where the sessions differ:
+    gs_status launch_rank(const Frame& f, Device& d, const gs_partition& p, const gs_render_outputs& o, bool direct);
+    gs_status read_back_session(const Frame& f, Device& d);
+    void note_pass(Shot& c);
+
+    gs_status views_form_check() const {  // (a views session's scene)
+        gs_scene_info si{};
+        const gs_status s = gs_device_scene_info(dev[0].scene, &si);
+        if (s != GS_OK || !(si.feat & 512)) return s;
+        return fail(GS_ERR_UNSUPPORTED, "the scene needs the catch-all kernel, which has no views form");
+    }
     gs_status accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk);
-    void accum_end();
-    // The tile (or -1) of rank `rank`'s slot `slot`, and the slots the rank holds.
-    int64_t rank_slots(int rank) const;
-    int32_t slot_tile(int rank, int64_t slot) const;
-    // Moves the sums between the ranks' packed buffers and an [H][W][3] image (to_image or back).
-    gs_status permute_sums(double* image, bool to_image);
-    // views: a views adaptation (cam is then the tall frame's camera; the arguments are checked by
-    // the caller, gs_views_check)
+    gs_status accum_alloc();
+    // (views: checked by the caller, gs_views_check, which gives the tall frame's camera: `tall`, or `cam`)
+    gs_status views_accum_begin(const gs_camera& tall, const gs_view* views, uint32_t n_views, uint32_t chunk);
     gs_status adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                           const gs_view* views = nullptr, uint32_t n_views = 0);
-    gs_status adapt_open(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, bool round_robin);
-    void adapt_end();
-    // What gs_multi_adapt_* and gs_multi_views_adapt_* share, on the open adaptation's frame (the
-    // tall one for views): a pass, the maps, the state down (sums may be NULL) and, behind
-    // adapt_begin, the state up.
+    gs_status adapt_alloc(const GsRoundLayout& l);
+    // What gs_multi_adapt_* and gs_multi_views_adapt_* share, on the open adaptation's frame (the tall one
+    // for views): a pass, the maps, the state down (sums may be NULL) and, behind adapt_begin, the state up.
     gs_status adapt_pass(uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats);
     gs_status adapt_maps(uint32_t* samples, float* rel_error);
     gs_status adapt_download(double* sums, uint32_t* state);
     gs_status adapt_fill(uint32_t rounds_done, const double* sums, const uint32_t* state, const gs_counters* counters);
+
     // The packed pixels of rank `rank` as its launches see them (gs_partition_capacity): `cap` under
     // a plan, fewer for the later ranks of a round-robin partition -- the size the rank's round
-    // state is laid out for.
+    // state is laid out for, and tw * part_th times the tile slots it holds.
     int64_t rank_cap(int rank, const gs_camera& cam) const {
-        if (!order.empty()) return cap;
-        gs_partition p{rank, (int32_t)dev.size(), tw, th, nullptr, 0, 0};
-        return std::max<int64_t>(0, gs_partition_capacity(&cam, &p));
+        const gs_partition p = part(rank);
+        return order.empty() ? std::max<int64_t>(0, gs_partition_capacity(&cam, &p)) : cap;
     }
-    bool adapt_finished() const { return ad_rounds > 0 && (ad_active == 0 || ad_rounds >= ad_R); }
+    gs_partition part(int rank) const {  // rank's share of the cached partition, as its launches take it
+        return {rank, (int32_t)dev.size(), tw, part_th, order.empty() ? nullptr : (const int32_t*)dev[rank].order.p, slots, 0};
+    }
     // Rank `rank`'s packed array of `elem`-byte records <-> the [H][W] image of them (to_image or
     // back; going back, slots outside the image keep what `packed` holds).
     void permute_rank(int rank, const gs_camera& cam, uint8_t* image, uint8_t* packed, size_t elem, bool to_image) const;
+    // An accumulation's sums: the ranks' packed buffers <-> the [H][W][3] image of frame `cam`.
+    gs_status permute_sums(const gs_camera& cam, double* image, bool to_image);
 };
 
-gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_ms, bool round_robin) {
-    if (part_ready && part_rr == round_robin && std::memcmp(&part_cam, cam, sizeof(gs_camera)) == 0) return GS_OK;
+// The one place that decides whether a call may proceed under the open session, and refuses it.
+gs_status gs_multi::admit(Call call, Session s) const {
+    if (call != Call::Begin && open == s) return GS_OK;
+    if (call == Call::Pass || call == Call::Other) {
+        static const char* const what[] = {"", "accumulation", "views accumulation", "adaptation", "views adaptation"};
+        static const char* const begin[] = {"", "gs_multi_accum_begin", "gs_multi_views_accum_begin",
+                                            "gs_multi_adapt_begin", "gs_multi_views_adapt_begin"};
+        std::string msg = std::string("no ") + what[(int)s] + " is open";
+        if (call == Call::Pass) msg += std::string(": ") + begin[(int)s] + " first";
+        return fail(GS_ERR_ARG, msg);
+    }
+    // A begin or a one-shot frame: nothing may be open (a new partition would invalidate what the session
+    // holds in packed order: the sums, the round state, the views' sums at their own tile height).
+    static const char* const refusal[] = {"", "an accumulation is open: gs_multi_accum_end first",
+                                          "a views accumulation is open: gs_multi_views_accum_end first",
+                                          "an adaptation is open: gs_multi_adapt_end first",
+                                          "a views adaptation is open: gs_multi_views_adapt_end first"};
+    if (open == Session::None) return GS_OK;
+    std::string msg = refusal[(int)open];
+    // (opened twice: "already"; a views adaptation begins as an adaptation: over one it is told
+    // "already" too, and over itself the plain refusal)
+    const bool twice = open == s || (open == Session::Adapt && s == Session::ViewsAdapt);
+    if (call == Call::Begin && twice && open != Session::ViewsAdapt) msg.insert(msg.find("open"), "already ");
+    return fail(GS_ERR_ARG, msg);
+}
+
+void gs_multi::close_session() {
+    DeviceGuard guard;
+    for (auto& d : dev) {
+        (void)hipSetDevice(d.id);
+        if (d.stream && !comms_broken) (void)hipStreamSynchronize(d.stream);
+        d.acc.release();
+        d.ad.release();
+    }
+    acc = AccumState{};
+    va = ViewsAccumState{};
+    ad = AdaptState{};
+    open = Session::None;
+}
+
+gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_ms, bool round_robin, int32_t tile_h) {
+    if (part_ready && part_rr == round_robin && part_th == tile_h && std::memcmp(&part_cam, cam, sizeof(gs_camera)) == 0)
+        return GS_OK;
     const auto t0 = std::chrono::steady_clock::now();
     const int n = (int)dev.size();
     part_ready = false;
@@ -351,121 +446,127 @@ gs_status gs_multi::partition(const gs_camera* cam, uint64_t seed, double* plan_
     slots = 0;
     if (plan && n > 1 && !round_robin) {
         HIPOK(hipSetDevice(dev[0].id));
-        gs_status s = gs_plan_tiles(dev[0].scene, cam, seed, n, tw, th, nullptr, 0, &slots);
+        gs_status s = gs_plan_tiles(dev[0].scene, cam, seed, n, tw, tile_h, nullptr, 0, &slots);
         if (s != GS_OK) return s;
         order.resize((size_t)slots * n);
-        s = gs_plan_tiles(dev[0].scene, cam, seed, n, tw, th, order.data(), (int64_t)order.size(), &slots);
+        s = gs_plan_tiles(dev[0].scene, cam, seed, n, tw, tile_h, order.data(), (int64_t)order.size(), &slots);
         if (s != GS_OK) return s;
         for (auto& d : dev) {
             HIPOK(hipSetDevice(d.id));
             GROW(d.order, order.size() * sizeof(int32_t));
             HIPOK(hipMemcpy(d.order.p, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
-        cap = (int64_t)slots * tw * th;
+        cap = (int64_t)slots * tw * tile_h;
     } else {
-        gs_partition p0{0, n, tw, th, nullptr, 0, 0};
+        gs_partition p0{0, n, tw, tile_h, nullptr, 0, 0};
         cap = gs_partition_capacity(cam, &p0);  // rank 0 holds the most tiles
         if (cap < 0) return fail(GS_ERR_ARG, "bad partition");
     }
     part_cam = *cam;
     part_rr = round_robin;
+    part_th = tile_h;
     part_ready = true;
-    *plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (plan_ms) *plan_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return GS_OK;
 }
 
-gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
-                           const gs_multi_outputs* out, gs_stats* stats, uint32_t pass_samples, bool adapt,
-                           uint32_t adapt_rounds, const ViewsCall* vw, const ViewsPass* vp) {
-    if (!cam || !ss) return fail(GS_ERR_ARG, "null argument");
+// ---------------------------------------------------------------- a frame, stage by stage
+gs_status gs_multi::render(const Frame& f, const gs_multi_outputs* out, gs_stats* stats) {
+    gs_status s = check_frame(f, out);
+    if (s != GS_OK) return s;
+    DeviceGuard guard;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int n = (int)dev.size();
+    Shot c{f, out};
+    c.st.render_ms_min = c.st.kernel_ms_min = 1e300;
+    c.want_rgb = !out || out->rgb;
+    c.want8 = out && (out->rgb8 || out->ppm_text);
+    c.W = f.cam->image_width, c.H = f.cam->image_height;
+    // One device and no collective: the render writes the frame itself (no packed tiles,
+    // no unpack: C1 saved the unpack kernel and a stream gap, ~20 us of a 0.9 ms frame).
+    c.direct = n == 1 && comms.empty();
+    // (direct without PPM text: nothing after the render to time, one stream marker fewer)
+    c.timed_tail = !c.direct || (out && out->ppm_text);
+    if ((s = prepare(c)) != GS_OK || (s = launch(c)) != GS_OK || (s = gather(c)) != GS_OK ||
+        (s = unpack(c)) != GS_OK || (s = wait(c)) != GS_OK)
+        return s;
+    note_pass(c);
+    c.st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c.st.algorithmic_bytes = algorithmic_bytes(c.st.counters);
+    c.st.gathered_bytes = comms.empty() && !copy_gather
+                              ? 0
+                              : (uint64_t)n * (uint64_t)cap * ((c.want_rgb ? 12u : 0u) + (c.want8 ? 3u : 0u));
+    c.st.num_gpus = n;
+    if (stats) *stats = c.st;
+    return GS_OK;
+}
+
+gs_status gs_multi::check_frame(const Frame& f, const gs_multi_outputs* out) const {
+    const gs_camera* cam = f.cam;
+    if (!cam || !f.ss) return fail(GS_ERR_ARG, "null argument");
     if (out && !out->rgb && !out->rgb8 && !out->ppm_text) return fail(GS_ERR_ARG, "no output requested");
     if (out && out->ppm_text && !out->ppm_len) return fail(GS_ERR_ARG, "ppm_text without ppm_len");
     if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
     if (out && out->ppm_text && out->ppm_capacity < gs_ppm_max_bytes(cam->image_width, cam->image_height))
         return fail(GS_ERR_ARG, "ppm_capacity below gs_ppm_max_bytes");
     if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
-    if (acc_open && !pass_samples)  // (a new plan would invalidate the packed sums)
-        return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
-    if (ad_open && !adapt)  // (likewise: the round state is in the plan's packed order)
-        return fail(GS_ERR_ARG, vd_open ? "a views adaptation is open: gs_multi_views_adapt_end first"
-                                        : "an adaptation is open: gs_multi_adapt_end first");
-    if (va_open && !vp)  // (likewise: the views' sums are in the packed order of its own tile height)
-        return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
-    DeviceGuard guard;
-    const auto t0 = std::chrono::steady_clock::now();
+    return admit(Call::Frame, f.session);
+}
+
+gs_status gs_multi::prepare(Shot& c) {
+    const Frame& f = c.f;
     const int n = (int)dev.size();
-    double plan_ms = 0.0;
-    gs_status s = partition(cam, seed, &plan_ms, vw != nullptr);
+    gs_status s = partition(f.cam, f.seed, &c.st.setup_ms, f.views != nullptr, f.th);
     if (s != GS_OK) return s;
-    {
-        // The scenes' placement pilots (first frame, launch.cpp, run before the first launch):
-        // launched on every device before any is waited for, outside the timed render.
-        std::vector<gs_device_scene*> sc(n);
-        std::vector<void*> st(n);
-        for (int i = 0; i < n; i++) sc[i] = dev[i].scene, st[i] = dev[i].stream;
-        const auto tp = std::chrono::steady_clock::now();
-        int ran = 0;
-        // (a views call: view 0's own camera and frame)
-        s = gs_placement_prepare(sc.data(), ids.data(), st.data(), n, vw ? &vw->views[0].cam : cam, ss, &ran);
-        if (s != GS_OK) return s;
-        if (ran) plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
-    }
-    const bool want_rgb = !out || out->rgb;
-    const bool want8 = out && (out->rgb8 || out->ppm_text);
-    const int64_t W = cam->image_width, H = cam->image_height;
+    // The scenes' placement pilots (first frame, launch.cpp, run before the first launch):
+    // launched on every device before any is waited for, outside the timed render.
+    std::vector<gs_device_scene*> sc(n);
+    std::vector<void*> st(n);
+    for (int i = 0; i < n; i++) sc[i] = dev[i].scene, st[i] = dev[i].stream;
+    const auto tp = std::chrono::steady_clock::now();
+    int ran = 0;
+    // (a views frame: view 0's own camera and frame)
+    s = gs_placement_prepare(sc.data(), ids.data(), st.data(), n, f.views ? &f.views[0].cam : f.cam, f.ss, &ran);
+    if (s != GS_OK) return s;
+    if (ran) c.st.setup_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
+    // the first device's frame and every rank's packed tiles and counters
     have_rgb = have_rgb8 = false;
+    HIPOK(hipSetDevice(dev[0].id));
+    if (c.want_rgb) GROW(frame, c.W * c.H * 12);
+    if (c.want8) GROW(frame8, c.W * c.H * 3);
+    for (auto& d : dev) {
+        HIPOK(hipSetDevice(d.id));
+        if (c.want_rgb && !c.direct) GROW(d.packed, cap * 12);
+        if (c.want8 && !c.direct) GROW(d.packed8, cap * 3);
+        GROW(d.cnt, sizeof(gs_counters));  // (zeroed by the launch's parameter kernel)
+    }
+    return GS_OK;
+}
 
-    // One device and no collective: the render writes the frame itself (no packed tiles,
-    // no unpack: C1 saved the unpack kernel and a stream gap, ~20 us of a 0.9 ms frame).
-    const bool direct = n == 1 && comms.empty();
-    Device& d0 = dev[0];
-    HIPOK(hipSetDevice(d0.id));
-    if (want_rgb) GROW(frame, W * H * 12);
-    if (want8) GROW(frame8, W * H * 3);
-
-    // Render: every device its own tiles, concurrently (launches are asynchronous).
+// Render: every device its own tiles, concurrently (launches are asynchronous).
+gs_status gs_multi::launch(Shot& c) {
+    const int n = (int)dev.size();
     for (int i = 0; i < n; i++) {
         Device& d = dev[i];
         HIPOK(hipSetDevice(d.id));
-        if (want_rgb && !direct) GROW(d.packed, cap * 12);
-        if (want8 && !direct) GROW(d.packed8, cap * 3);
-        GROW(d.cnt, sizeof(gs_counters));  // (zeroed by the launch's parameter kernel)
-        gs_partition p{i, n, tw, th, order.empty() ? nullptr : (const int32_t*)d.order.p, slots, 0};
-        gs_render_outputs o{want_rgb ? (float*)(direct ? frame.p : d.packed.p) : nullptr,
-                            want8 ? (uint8_t*)(direct ? frame8.p : d.packed8.p) : nullptr, nullptr};
+        const gs_partition p = part(i);
+        const gs_render_outputs o{c.want_rgb ? (float*)(c.direct ? frame.p : d.packed.p) : nullptr,
+                                  c.want8 ? (uint8_t*)(c.direct ? frame8.p : d.packed8.p) : nullptr, nullptr};
         HIPOK(hipEventRecord(d.ev[0], d.stream));
-        if (adapt) {
-            const gs_round_outputs ro{o.rgb, o.rgb8, (uint32_t*)d.map_samples.p, (float*)d.map_error.p};
-            s = vw ? gs_render_tiles_views_rounds_timed_async(d.scene, vw->views, vw->n, ss, &p, ad_rounds, adapt_rounds,
-                                                              d.rstate.p, (int64_t)d.rstate.bytes, &ro,
-                                                              (gs_counters*)d.cnt.p, d.stream, d.ev[2], d.ev[3], direct,
-                                                              ad_fresh)
-                   : gs_render_tiles_rounds_timed_async(d.scene, cam, ss, seed, &p, ad_rounds, adapt_rounds, d.rstate.p,
-                                                        (int64_t)d.rstate.bytes, &ro, (gs_counters*)d.cnt.p, d.stream,
-                                                        d.ev[2], d.ev[3], direct, ad_fresh);
-        } else if (pass_samples) {
-            HIPOK(hipMemsetAsync(d.delta.p, 0, (size_t)gs_pass_delta_blocks(cap) * 8, d.stream));
-            s = gs_render_tiles_pass_timed_async(d.scene, cam, pass_samples, seed, &p, (uint32_t)acc_samples, acc_chunk,
-                                                 (double*)d.sums.p, (double*)d.delta.p, &o, (gs_counters*)d.cnt.p,
-                                                 d.stream, d.ev[2], d.ev[3], direct, true);
-        } else if (vp) {  // (every slot's partial is written by the pass's combine: no memset)
-            s = gs_render_tiles_views_pass_timed_async(d.scene, vw->views, vw->n, va_samples.data(), vp->selected,
-                                                       ss->batch_size, vw->chunk, &p, (double*)d.sums.p, &o,
-                                                       (double*)d.delta.p, (gs_counters*)d.cnt.p, d.stream, d.ev[2],
-                                                       d.ev[3], direct, true);
-        } else if (vw) {
-            s = gs_render_tiles_views_timed_async(d.scene, vw->views, vw->n, ss->batch_size, vw->chunk, &p, &o,
-                                                  (gs_counters*)d.cnt.p, d.stream, d.ev[2], d.ev[3], direct, true);
-        } else {
-            s = gs_render_tiles_timed_async(d.scene, cam, ss, seed, &p, &o, (gs_counters*)d.cnt.p, d.stream, d.ev[2],
-                                            d.ev[3], direct, true);
-        }
+        const gs_status s = launch_rank(c.f, d, p, o, c.direct);
         if (s != GS_OK) return s;
         HIPOK(hipEventRecord(d.ev[1], d.stream));
     }
+    return GS_OK;
+}
+
+gs_status gs_multi::gather(Shot& c) {
+    const int n = (int)dev.size();
+    const bool want_rgb = c.want_rgb, want8 = c.want8;
+    Device& d0 = dev[0];
     HIPOK(hipSetDevice(d0.id));
-    const void* src = want_rgb ? d0.packed.p : nullptr;
-    const void* src8 = want8 ? d0.packed8.p : nullptr;
+    c.src = want_rgb ? d0.packed.p : nullptr;
+    c.src8 = want8 ? d0.packed8.p : nullptr;
     if (!comms.empty()) {
         // One grouped RCCL gather of the packed tiles to the first device (rank-major, as
         // gs_unpack_tiles_part_async reads them).
@@ -492,8 +593,8 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         if (rc != ncclSuccess || rc2 != ncclSuccess)
             return collective_failed(std::string("ncclGather: ") + R.error_string(rc != ncclSuccess ? rc : rc2));
         HIPOK(hipSetDevice(d0.id));
-        src = gathered.p;
-        src8 = gathered8.p;
+        c.src = gathered.p;
+        c.src8 = gathered8.p;
     } else if (copy_gather) {
         // The test mode's gather (gs_debug_set_multi_same_device): each rank's packed tiles
         // copied on its own stream into its rank-major slot of the first device's buffer,
@@ -513,19 +614,23 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         }
         HIPOK(hipSetDevice(d0.id));
         for (int i = 1; i < n; i++) HIPOK(hipStreamWaitEvent(d0.stream, dev[i].ev[4], 0));
-        src = gathered.p;
-        src8 = gathered8.p;
+        c.src = gathered.p;
+        c.src8 = gathered8.p;
     }  // (no collective: the unpack is timed from the render's end event, ev[1])
-    gs_partition pu{0, n, tw, th, order.empty() ? nullptr : (const int32_t*)d0.order.p, slots, 0};
-    if (want_rgb && !direct) {
-        s = gs_unpack_tiles_part_async(cam, &pu, cap, src, frame.p, 12, d0.stream);
-        if (s != GS_OK) return s;
-    }
-    if (want8 && !direct) {
-        s = gs_unpack_tiles_part_async(cam, &pu, cap, src8, frame8.p, 3, d0.stream);
-        if (s != GS_OK) return s;
-    }
-    if (out && out->ppm_text) {
+    return GS_OK;
+}
+
+// (on the first device, which the gather leaves current)
+gs_status gs_multi::unpack(Shot& c) {
+    const gs_camera* cam = c.f.cam;
+    Device& d0 = dev[0];
+    const gs_partition pu = part(0);
+    gs_status s = GS_OK;
+    if (c.want_rgb && !c.direct) s = gs_unpack_tiles_part_async(cam, &pu, cap, c.src, frame.p, 12, d0.stream);
+    if (s != GS_OK) return s;
+    if (c.want8 && !c.direct) s = gs_unpack_tiles_part_async(cam, &pu, cap, c.src8, frame8.p, 3, d0.stream);
+    if (s != GS_OK) return s;
+    if (c.out && c.out->ppm_text) {
         const int64_t need = gs_ppm_max_bytes(cam->image_width, cam->image_height);
         const int64_t sb = gs_ppm_scratch_bytes(cam->image_width, cam->image_height);
         GROW(text, need);
@@ -535,50 +640,47 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
                                 (int64_t*)len.p, scratch.p, sb, d0.stream);
         if (s != GS_OK) return s;
     }
-    // (direct without PPM text: nothing after the render to time, one stream marker fewer)
-    const bool timed_tail = !direct || (out && out->ppm_text);
-    if (timed_tail) HIPOK(hipEventRecord(d0.ev[5], d0.stream));
+    // ... and behind the frame the read-backs, so that the host's wait is the only synchronisation
+    if (c.timed_tail) HIPOK(hipEventRecord(d0.ev[5], d0.stream));
     for (auto& d : dev) {
         HIPOK(hipSetDevice(d.id));
         HIPOK(hipMemcpyAsync(d.h_cnt, d.cnt.p, sizeof(gs_counters), hipMemcpyDeviceToHost, d.stream));
-        if (adapt)  // (the active count the next pass's clip needs: the pass's one read-back)
-            HIPOK(hipMemcpyAsync(d.h_summary, (const char*)d.rstate.p + gs_round_layout(0, ad_R).summary,
-                                 kRoundSummaryWords * 8, hipMemcpyDeviceToHost, d.stream));
-        if (pass_samples)
-            HIPOK(hipMemcpyAsync(d.h_delta, d.delta.p, (size_t)gs_pass_delta_blocks(cap) * 8, hipMemcpyDeviceToHost,
-                                 d.stream));
-        if (vp)
-            HIPOK(hipMemcpyAsync(d.h_delta, d.delta.p, (size_t)(cap / ((int64_t)tw * th)) * 8, hipMemcpyDeviceToHost,
-                                 d.stream));
+        if ((s = read_back_session(c.f, d)) != GS_OK) return s;
     }
-    // Wait, then results.
-    gs_counters total{};
-    double rmax = 0.0, rmin = 1e300, kmax = 0.0, kmin = 1e300;
-    for (int i = 0; i < n; i++) {
-        Device& d = dev[i];
+    return GS_OK;
+}
+
+// Wait, then the counters and the timings.
+gs_status gs_multi::wait(Shot& c) {
+    // (an adaptation's counters run on from pass to pass)
+    const bool running = (c.f.session == Session::Adapt || c.f.session == Session::ViewsAdapt) && !ad.fresh;
+    for (auto& d : dev) {
         HIPOK(hipSetDevice(d.id));
         HIPOK(hipStreamSynchronize(d.stream));
-        add_counters(total, *d.h_cnt);
+        add_counters(c.st.counters, *d.h_cnt);
         float ms = 0.0f, kms = 0.0f;
         HIPOK(hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
         HIPOK(hipEventElapsedTime(&kms, d.ev[2], d.ev[3]));
-        const uint64_t paths_before = adapt && !ad_fresh ? d.ad_paths : 0u;  // (an adaptation's counters run on)
-        gs_device_scene_note_frame(d.scene, (double)kms, d.h_cnt->paths - paths_before);
-        d.ad_paths = d.h_cnt->paths;
-        rmax = std::max(rmax, (double)ms);
-        rmin = std::min(rmin, (double)ms);
-        kmax = std::max(kmax, (double)kms);
-        kmin = std::min(kmin, (double)kms);
+        gs_device_scene_note_frame(d.scene, (double)kms, d.h_cnt->paths - (running ? d.ad.paths : 0u));
+        d.ad.paths = d.h_cnt->paths;
+        c.st.render_ms_max = std::max(c.st.render_ms_max, (double)ms);
+        c.st.render_ms_min = std::min(c.st.render_ms_min, (double)ms);
+        c.st.kernel_ms_max = std::max(c.st.kernel_ms_max, (double)kms);
+        c.st.kernel_ms_min = std::min(c.st.kernel_ms_min, (double)kms);
     }
+    Device& d0 = dev[0];
     HIPOK(hipSetDevice(d0.id));
     float gms = 0.0f;
-    if (timed_tail) HIPOK(hipEventElapsedTime(&gms, comms.empty() && !copy_gather ? d0.ev[1] : d0.ev[4], d0.ev[5]));
-    have_rgb = want_rgb;
-    have_rgb8 = want8;
-    frame_w = cam->image_width;
-    frame_h = cam->image_height;
-    if (out && out->rgb) HIPOK(hipMemcpy(out->rgb, frame.p, (size_t)(W * H * 12), hipMemcpyDeviceToHost));
-    if (out && out->rgb8) HIPOK(hipMemcpy(out->rgb8, frame8.p, (size_t)(W * H * 3), hipMemcpyDeviceToHost));
+    if (c.timed_tail) HIPOK(hipEventElapsedTime(&gms, comms.empty() && !copy_gather ? d0.ev[1] : d0.ev[4], d0.ev[5]));
+    c.st.gather_ms = gms;
+    // the host outputs
+    const gs_multi_outputs* out = c.out;
+    have_rgb = c.want_rgb;
+    have_rgb8 = c.want8;
+    frame_w = (int32_t)c.W;
+    frame_h = (int32_t)c.H;
+    if (out && out->rgb) HIPOK(hipMemcpy(out->rgb, frame.p, (size_t)(c.W * c.H * 12), hipMemcpyDeviceToHost));
+    if (out && out->rgb8) HIPOK(hipMemcpy(out->rgb8, frame8.p, (size_t)(c.W * c.H * 3), hipMemcpyDeviceToHost));
     if (out && out->ppm_text) {
         int64_t l = 0;
         HIPOK(hipMemcpy(&l, len.p, 8, hipMemcpyDeviceToHost));
@@ -586,337 +688,286 @@ gs_status gs_multi::render(const gs_camera* cam, const gs_sample_settings* ss, u
         HIPOK(hipMemcpy(out->ppm_text, text.p, (size_t)l, hipMemcpyDeviceToHost));
         *out->ppm_len = l;
     }
-    if (pass_samples) {
+    return GS_OK;
+}
+
+// ---------------------------------------------------------------- where the sessions differ
+// One rank's launch, between its render events.
+gs_status gs_multi::launch_rank(const Frame& f, Device& d, const gs_partition& p, const gs_render_outputs& o,
+                                bool direct) {
+    gs_counters* cnt = (gs_counters*)d.cnt.p;
+    switch (f.session) {
+    case Session::None:
+        return f.views ? gs_render_tiles_views_timed_async(d.scene, f.views, f.n_views, f.ss->batch_size, f.chunk, &p, &o,
+                                                           cnt, d.stream, d.ev[2], d.ev[3], direct, true)
+                       : gs_render_tiles_timed_async(d.scene, f.cam, f.ss, f.seed, &p, &o, cnt, d.stream, d.ev[2],
+                                                     d.ev[3], direct, true);
+    case Session::Accum:
+        HIPOK(hipMemsetAsync(d.acc.delta.p, 0, (size_t)gs_pass_delta_blocks(cap) * 8, d.stream));
+        return gs_render_tiles_pass_timed_async(d.scene, f.cam, f.ss->batch_size, f.seed, &p, (uint32_t)acc.samples,
+                                                acc.chunk, (double*)d.acc.sums.p, (double*)d.acc.delta.p, &o, cnt,
+                                                d.stream, d.ev[2], d.ev[3], direct, true);
+    case Session::ViewsAccum:  // (every slot's partial is written by the pass's combine: no memset)
+        return gs_render_tiles_views_pass_timed_async(d.scene, f.views, f.n_views, va.samples.data(), f.selected,
+                                                      f.ss->batch_size, f.chunk, &p, (double*)d.acc.sums.p, &o,
+                                                      (double*)d.acc.delta.p, cnt, d.stream, d.ev[2], d.ev[3], direct,
+                                                      true);
+    case Session::Adapt:
+    case Session::ViewsAdapt: {
+        const gs_round_outputs ro{o.rgb, o.rgb8, (uint32_t*)d.ad.map_samples.p, (float*)d.ad.map_error.p};
+        return f.views ? gs_render_tiles_views_rounds_timed_async(d.scene, f.views, f.n_views, f.ss, &p, ad.rounds,
+                                                                  f.rounds, d.ad.rstate.p, (int64_t)d.ad.rstate.bytes,
+                                                                  &ro, cnt, d.stream, d.ev[2], d.ev[3], direct, ad.fresh)
+                       : gs_render_tiles_rounds_timed_async(d.scene, f.cam, f.ss, f.seed, &p, ad.rounds, f.rounds,
+                                                            d.ad.rstate.p, (int64_t)d.ad.rstate.bytes, &ro, cnt,
+                                                            d.stream, d.ev[2], d.ev[3], direct, ad.fresh);
+    }
+    }
+    return GS_OK;
+}
+
+// One rank's read-backs behind the frame's counters: what note_pass reads after the wait.
+gs_status gs_multi::read_back_session(const Frame& f, Device& d) {
+    switch (f.session) {
+    case Session::None: break;
+    case Session::Accum:
+        HIPOK(hipMemcpyAsync(d.acc.h_delta, d.acc.delta.p, (size_t)gs_pass_delta_blocks(cap) * 8,
+                             hipMemcpyDeviceToHost, d.stream));
+        break;
+    case Session::ViewsAccum:
+        HIPOK(hipMemcpyAsync(d.acc.h_delta, d.acc.delta.p, (size_t)(cap / ((int64_t)tw * part_th)) * 8,
+                             hipMemcpyDeviceToHost, d.stream));
+        break;
+    case Session::Adapt:
+    case Session::ViewsAdapt:  // (the active count the next pass's clip needs: the pass's one read-back)
+        HIPOK(hipMemcpyAsync(d.ad.h_summary, (const char*)d.ad.rstate.p + gs_round_layout(0, ad.R).summary,
+                             kRoundSummaryWords * 8, hipMemcpyDeviceToHost, d.stream));
+        break;
+    }
+    return GS_OK;
+}
+
+// The open session's bookkeeping after a pass (c.st.counters: the ranks' counters, made this pass's own).
+void gs_multi::note_pass(Shot& c) {
+    const Frame& f = c.f;
+    const int n = (int)dev.size();
+    switch (f.session) {
+    case Session::None: break;
+    case Session::Accum: {
         // the pass's change: every rank's per-block partials in index order, the ranks in rank order
         double change = 0.0;
         const int64_t nb = gs_pass_delta_blocks(cap);
         for (int i = 0; i < n; i++)
-            for (int64_t b = 0; b < nb; b++) change += dev[i].h_delta[b];
-        acc_last_delta = change / ((double)W * (double)H * 3.0);
-        gs_counters add = total;
-        if (acc_samples != 0) add.pixels = 0;  // (the kernel counts a pixel at chunk 0 of every pass)
-        add_counters(acc_counters, add);
-        acc_samples += pass_samples;
-        acc_passes += 1;
+            for (int64_t b = 0; b < nb; b++) change += dev[i].acc.h_delta[b];
+        acc.last_delta = change / ((double)c.W * (double)c.H * 3.0);
+        gs_counters add = c.st.counters;
+        if (acc.samples != 0) add.pixels = 0;  // (the kernel counts a pixel at chunk 0 of every pass)
+        add_counters(acc.counters, add);
+        acc.samples += f.ss->batch_size;
+        acc.passes += 1;
+        break;
     }
-    if (vp) {
+    case Session::ViewsAccum: {
         // the selected views' change: a view's per-slot partials rank after rank, each rank's in
         // slot order (round-robin: rank i's slot sl holds tile i + sl n, which lies in one view)
-        const int64_t vh = va_views[0].cam.image_height, tx = (W + tw - 1) / tw, nt = tx * (H / th);
-        std::vector<double> change(vw->n, 0.0);
+        const int64_t tpx = (int64_t)tw * part_th, vh = va.views[0].cam.image_height, tx = (c.W + tw - 1) / tw;
+        const int64_t nt = tx * (c.H / part_th);
+        std::vector<double> change(f.n_views, 0.0);
         for (int i = 0; i < n; i++) {
-            const int64_t ns = rank_cap(i, *cam) / ((int64_t)tw * th);
+            const int64_t ns = rank_cap(i, *f.cam) / tpx;
             for (int64_t sl = 0; sl < ns; sl++) {
                 const int64_t tile = i + sl * n;
-                if (tile < nt) change[(size_t)((tile / tx) * th / vh)] += dev[i].h_delta[sl];
+                if (tile < nt) change[(size_t)((tile / tx) * part_th / vh)] += dev[i].acc.h_delta[sl];
             }
         }
-        for (uint32_t v = 0; v < vw->n; v++)
-            if (!vp->selected || vp->selected[v]) {
-                va_delta[v] = change[v] / ((double)W * (double)vh * 3.0);
-                va_samples[v] += ss->batch_size;
+        for (uint32_t v = 0; v < f.n_views; v++)
+            if (!f.selected || f.selected[v]) {
+                va.delta[v] = change[v] / ((double)c.W * (double)vh * 3.0);
+                va.samples[v] += f.ss->batch_size;
             }
-        gs_counters add = total;
+        gs_counters add = c.st.counters;
         // (the kernel counts the selected views' pixels at chunk 0 of every pass; they all start
         // at sample 0 or none does)
-        if (vp->base != 0) add.pixels = 0;
-        add_counters(va_counters, add);
-        va_passes += 1;
+        if (f.base != 0) add.pixels = 0;
+        add_counters(va.counters, add);
+        va.passes += 1;
+        break;
     }
-    if (adapt) {
-        ad_active = ad_samples_total = ad_samples_max = 0;
+    case Session::Adapt:
+    case Session::ViewsAdapt: {
+        ad.active = ad.samples_total = ad.samples_max = 0;
         for (int i = 0; i < n; i++) {
-            ad_active += dev[i].h_summary[0];
-            ad_samples_total += dev[i].h_summary[1];
-            ad_samples_max = std::max<uint64_t>(ad_samples_max, dev[i].h_summary[2]);
+            ad.active += dev[i].ad.h_summary[0];
+            ad.samples_total += dev[i].ad.h_summary[1];
+            ad.samples_max = std::max<uint64_t>(ad.samples_max, dev[i].ad.h_summary[2]);
         }
         // this pass alone: the ranks' running counters minus their sum after the last pass
-        const gs_counters before = ad_fresh ? gs_counters{} : ad_dev;
-        ad_dev = total;
-        ad_counters = ad_base;
-        add_counters(ad_counters, ad_dev);
+        const gs_counters before = ad.fresh ? gs_counters{} : ad.dev;
+        ad.dev = c.st.counters;
+        ad.counters = ad.base;
+        add_counters(ad.counters, ad.dev);
         const uint64_t* pb = (const uint64_t*)&before;
-        uint64_t* pt = (uint64_t*)&total;
+        uint64_t* pt = (uint64_t*)&c.st.counters;
         for (size_t k = 0; k < sizeof(gs_counters) / sizeof(uint64_t); k++) pt[k] -= pb[k];
-        ad_fresh = false;
-        ad_rounds += adapt_rounds;
+        ad.fresh = false;
+        ad.rounds += f.rounds;
+        break;
     }
-    const auto t1 = std::chrono::steady_clock::now();
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->counters = total;
-        stats->setup_ms = plan_ms;
-        stats->total_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-        stats->render_ms_max = rmax;
-        stats->render_ms_min = rmin;
-        stats->kernel_ms_max = kmax;
-        stats->kernel_ms_min = kmin;
-        stats->gather_ms = gms;
-        stats->algorithmic_bytes = algorithmic_bytes(total);
-        stats->gathered_bytes =
-            comms.empty() && !copy_gather ? 0 : (uint64_t)n * (uint64_t)cap * ((want_rgb ? 12u : 0u) + (want8 ? 3u : 0u));
-        stats->num_gpus = n;
     }
-    return GS_OK;
 }
 
-// ---------------------------------------------------------------- progressive accumulation
-int64_t gs_multi::rank_slots(int rank) const {
-    if (!order.empty()) return slots;
-    gs_partition p{rank, (int32_t)dev.size(), tw, th, nullptr, 0, 0};
-    return gs_partition_capacity(&acc_cam, &p) / ((int64_t)tw * th);
+void gs_multi::permute_rank(int rank, const gs_camera& cam, uint8_t* image, uint8_t* packed, size_t elem,
+                            bool to_image) const {
+    const int64_t W = cam.image_width, H = cam.image_height, tpx = (int64_t)tw * part_th;
+    const int64_t tx = (W + tw - 1) / tw, nt = tx * ((H + part_th - 1) / part_th);
+    const int64_t ns = std::min(cap, rank_cap(rank, cam)) / tpx;
+    for (int64_t sl = 0; sl < ns; sl++) {
+        const int64_t pos = rank + sl * (int64_t)dev.size(), tile = order.empty() ? pos : order[(size_t)pos];
+        if (tile < 0 || tile >= nt) continue;
+        const int64_t x0 = (tile % tx) * tw, y0 = (tile / tx) * part_th;
+        const int64_t nx = std::min<int64_t>(tw, W - x0);
+        for (int64_t y = 0; y < part_th && y0 + y < H; y++) {
+            uint8_t* img = image + (size_t)((y0 + y) * W + x0) * elem;
+            uint8_t* pk = packed + (size_t)(sl * tpx + y * tw) * elem;
+            std::memcpy(to_image ? img : pk, to_image ? pk : img, (size_t)nx * elem);
+        }
+    }
 }
 
-int32_t gs_multi::slot_tile(int rank, int64_t slot) const {
-    const int64_t pos = rank + slot * (int64_t)dev.size();
-    return order.empty() ? (int32_t)pos : order[(size_t)pos];
-}
-
-gs_status gs_multi::accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk) {
-    if (acc_open) return fail(GS_ERR_ARG, "an accumulation is already open: gs_multi_accum_end first");
-    if (vd_open) return fail(GS_ERR_ARG, "a views adaptation is open: gs_multi_views_adapt_end first");
-    if (ad_open) return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
-    if (va_open) return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
-    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
-    if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
+// Checkpoints are not hot: each rank's packed sums cross to the host whole and are permuted there.
+gs_status gs_multi::permute_sums(const gs_camera& cam, double* image, bool to_image) {
     DeviceGuard guard;
-    double plan_ms = 0.0;
-    gs_status s = partition(cam, seed, &plan_ms);
-    if (s != GS_OK) return s;
-    if (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll) return fail(GS_ERR_ARG, "bad partition");
-    const size_t nb = (size_t)gs_pass_delta_blocks(cap);
-    for (auto& d : dev) {
-        HIPOK(hipSetDevice(d.id));
-        GROW(d.sums, cap * 24);
-        GROW(d.delta, nb * 8);
-        HIPOK(hipMemsetAsync(d.sums.p, 0, (size_t)cap * 24, d.stream));
-        if (d.h_delta) (void)hipHostFree(d.h_delta);
-        d.h_delta = nullptr;
-        if (hipHostMalloc((void**)&d.h_delta, nb * 8, hipHostMallocDefault) != hipSuccess)
-            return fail(GS_ERR_OOM, "hipHostMalloc of the pass's change failed");
-        HIPOK(hipStreamSynchronize(d.stream));
-    }
-    acc_cam = *cam;
-    acc_seed = seed;
-    acc_chunk = chunk ? chunk : 16u;
-    acc_samples = 0;
-    acc_passes = 0;
-    acc_last_delta = 0.0;
-    acc_counters = gs_counters{};
-    acc_open = true;
-    return GS_OK;
-}
-
-void gs_multi::accum_end() {
-    DeviceGuard guard;
-    for (auto& d : dev) {
-        (void)hipSetDevice(d.id);
-        if (d.stream && !comms_broken) (void)hipStreamSynchronize(d.stream);
-        d.sums.release();
-        d.delta.release();
-        if (d.h_delta) (void)hipHostFree(d.h_delta);
-        d.h_delta = nullptr;
-    }
-    acc_open = false;
-}
-
-// Checkpoints are not hot: each rank's packed sums cross to the host whole, and the tile
-// permutation runs there.
-gs_status gs_multi::permute_sums(double* image, bool to_image) {
-    DeviceGuard guard;
-    const int64_t W = acc_cam.image_width, H = acc_cam.image_height, tpx = (int64_t)tw * th;
-    const int64_t tx = (W + tw - 1) / tw, nt = tx * ((H + th - 1) / th);
     std::vector<double> packed((size_t)cap * 3);
     for (int i = 0; i < (int)dev.size(); i++) {
         Device& d = dev[i];
         HIPOK(hipSetDevice(d.id));
         HIPOK(hipStreamSynchronize(d.stream));
         if (to_image)
-            HIPOK(hipMemcpy(packed.data(), d.sums.p, packed.size() * 8, hipMemcpyDeviceToHost));
+            HIPOK(hipMemcpy(packed.data(), d.acc.sums.p, packed.size() * 8, hipMemcpyDeviceToHost));
         else
             std::fill(packed.begin(), packed.end(), 0.0);
-        const int64_t ns = std::min<int64_t>(rank_slots(i), cap / tpx);
-        for (int64_t sl = 0; sl < ns; sl++) {
-            const int64_t tile = slot_tile(i, sl);
-            if (tile < 0 || tile >= nt) continue;
-            const int64_t x0 = (tile % tx) * tw, y0 = (tile / tx) * th;
-            for (int64_t y = 0; y < th && y0 + y < H; y++) {
-                const int64_t nx = std::min<int64_t>(tw, W - x0);
-                double* img = image + ((y0 + y) * W + x0) * 3;
-                double* pk = packed.data() + (sl * tpx + y * tw) * 3;
-                if (to_image)
-                    std::memcpy(img, pk, (size_t)nx * 24);
-                else
-                    std::memcpy(pk, img, (size_t)nx * 24);
-            }
-        }
-        if (!to_image) HIPOK(hipMemcpy(d.sums.p, packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
+        permute_rank(i, cam, (uint8_t*)image, (uint8_t*)packed.data(), 24, to_image);
+        if (!to_image) HIPOK(hipMemcpy(d.acc.sums.p, packed.data(), packed.size() * 8, hipMemcpyHostToDevice));
     }
     return GS_OK;
 }
 
-// ---------------------------------------------------------------- progressive views
-// (the arguments are checked by the caller: gs_views_check)
-gs_status gs_multi::views_accum_begin(const gs_view* views, uint32_t n_views, uint32_t chunk) {
-    if (va_open) return fail(GS_ERR_ARG, "a views accumulation is already open: gs_multi_views_accum_end first");
-    if (acc_open) return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
-    if (vd_open) return fail(GS_ERR_ARG, "a views adaptation is open: gs_multi_views_adapt_end first");
-    if (ad_open) return fail(GS_ERR_ARG, "an adaptation is open: gs_multi_adapt_end first");
-    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
-    gs_scene_info si{};
-    gs_status s = gs_device_scene_info(dev[0].scene, &si);
+// ---------------------------------------------------------------- progressive accumulation
+gs_status gs_multi::accum_begin(const gs_camera* cam, uint64_t seed, uint32_t chunk) {
+    gs_status s = admit(Call::Begin, Session::Accum);
     if (s != GS_OK) return s;
-    if (si.feat & 512)
-        return fail(GS_ERR_UNSUPPORTED, "the scene needs the catch-all kernel, which has no views form");
-    gs_camera tall = views[0].cam;
-    tall.image_height = (int32_t)(n_views * (uint32_t)views[0].cam.image_height);
+    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
+    if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
     DeviceGuard guard;
-    // the accumulation's own tile height, so that no tile straddles two views; the cut is redone
-    // whatever camera the last frame had (the partition's cache does not know the tile height)
-    th_ctx = th;
-    th = gs_views_tile_h(views[0].cam.image_height, th_ctx);
-    part_ready = false;
-    double plan_ms = 0.0;
-    s = partition(&tall, 0, &plan_ms, true);
+    if ((s = partition(cam, seed, nullptr, false, th)) != GS_OK) return s;
+    if (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll) return fail(GS_ERR_ARG, "bad partition");
+    if ((s = accum_alloc()) != GS_OK) return close_session(), s;
+    acc.cam = *cam;
+    acc.seed = seed;
+    acc.chunk = chunk ? chunk : 16u;
+    open = Session::Accum;
+    return GS_OK;
+}
+
+gs_status gs_multi::accum_alloc() {
+    const size_t nb = (size_t)gs_pass_delta_blocks(cap);
+    for (auto& d : dev) {
+        HIPOK(hipSetDevice(d.id));
+        GROW(d.acc.sums, cap * 24);
+        GROW(d.acc.delta, nb * 8);
+        HIPOK(hipMemsetAsync(d.acc.sums.p, 0, (size_t)cap * 24, d.stream));
+        if (hipHostMalloc((void**)&d.acc.h_delta, nb * 8, hipHostMallocDefault) != hipSuccess)
+            return fail(GS_ERR_OOM, "hipHostMalloc of the pass's change failed");
+        HIPOK(hipStreamSynchronize(d.stream));
+    }
+    return GS_OK;
+}
+
+gs_status gs_multi::views_accum_begin(const gs_camera& tall, const gs_view* views, uint32_t n_views, uint32_t chunk) {
+    gs_status s = admit(Call::Begin, Session::ViewsAccum);
+    if (s != GS_OK) return s;
+    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
+    if ((s = views_form_check()) != GS_OK) return s;
+    DeviceGuard guard;
+    // the accumulation's own tile height, so that no tile straddles two views
+    const int32_t vth = gs_views_tile_h(views[0].cam.image_height, th);
+    s = partition(&tall, 0, nullptr, true, vth);
     if (s == GS_OK && (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll)) s = fail(GS_ERR_ARG, "bad partition");
-    const size_t nb = s == GS_OK ? (size_t)(cap / ((int64_t)tw * th)) : 0;
+    const size_t nb = s == GS_OK ? (size_t)(cap / ((int64_t)tw * vth)) : 0;
     for (size_t i = 0; s == GS_OK && i < dev.size(); i++) {
         Device& d = dev[i];
-        if (hipSetDevice(d.id) != hipSuccess || !d.sums.ensure((size_t)cap * 24) || !d.delta.ensure(nb * 8)) {
+        if (hipSetDevice(d.id) != hipSuccess || !d.acc.sums.ensure((size_t)cap * 24) || !d.acc.delta.ensure(nb * 8))
             s = fail(GS_ERR_OOM, "hipMalloc of the views' sums failed");
-            break;
-        }
-        if (d.h_delta) (void)hipHostFree(d.h_delta);
-        d.h_delta = nullptr;
-        if (hipHostMalloc((void**)&d.h_delta, nb * 8, hipHostMallocDefault) != hipSuccess)
+        else if (hipHostMalloc((void**)&d.acc.h_delta, nb * 8, hipHostMallocDefault) != hipSuccess)
             s = fail(GS_ERR_OOM, "hipHostMalloc of the pass's change failed");
-        else if (hipMemsetAsync(d.sums.p, 0, (size_t)cap * 24, d.stream) != hipSuccess ||
+        else if (hipMemsetAsync(d.acc.sums.p, 0, (size_t)cap * 24, d.stream) != hipSuccess ||
                  hipStreamSynchronize(d.stream) != hipSuccess)
             s = fail(GS_ERR_HIP, "zeroing the views' sums failed");
     }
-    va_open = true;  // (views_accum_end undoes a partial begin)
-    if (s != GS_OK) {
-        views_accum_end();
-        return s;
-    }
-    va_views.assign(views, views + n_views);
-    va_tall = tall;
-    acc_cam = tall;  // (permute_sums, rank_slots)
-    va_chunk = chunk ? chunk : 16u;
-    va_passes = 0;
-    va_samples.assign(n_views, 0u);
-    va_delta.assign(n_views, 0.0);
-    va_counters = gs_counters{};
+    if (s != GS_OK) return close_session(), s;
+    va.views.assign(views, views + n_views);
+    va.tall = tall;
+    va.th = vth;
+    va.chunk = chunk ? chunk : 16u;
+    va.samples.assign(n_views, 0u);
+    va.delta.assign(n_views, 0.0);
+    open = Session::ViewsAccum;
     return GS_OK;
 }
 
-void gs_multi::views_accum_end() {
-    DeviceGuard guard;
-    for (auto& d : dev) {
-        (void)hipSetDevice(d.id);
-        if (d.stream && !comms_broken) (void)hipStreamSynchronize(d.stream);
-        d.sums.release();
-        d.delta.release();
-        if (d.h_delta) (void)hipHostFree(d.h_delta);
-        d.h_delta = nullptr;
-    }
-    th = th_ctx;
-    part_ready = false;
-    va_open = false;
-}
-
-// ---------------------------------------------------------------- progressive adaptation
+// ---------------------------------------------------------------- progressive adaptation, plain and of views
 gs_status gs_multi::adapt_begin(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
                                 const gs_view* views, uint32_t n_views) {
-    if (!views) return adapt_open(cam, ss, seed, false);
-    if (vd_open || ad_open || acc_open || va_open) return adapt_open(cam, ss, seed, true);  // (its refusal)
-    gs_scene_info si{};
-    const gs_status si_s = gs_device_scene_info(dev[0].scene, &si);
-    if (si_s != GS_OK) return si_s;
-    if (si.feat & 512) return fail(GS_ERR_UNSUPPORTED, "the scene needs the catch-all kernel, which has no views form");
-    // the batch's own tile height, so that no tile straddles two views; the cut is redone whatever
-    // camera the last frame had (the partition's cache does not know the tile height)
-    const int32_t th_was = th;
-    th = gs_views_tile_h(views[0].cam.image_height, th_was);
-    part_ready = false;
-    const gs_status s = adapt_open(cam, ss, seed, true);
-    if (s != GS_OK) {
-        th = th_was;
-        part_ready = false;
-        return s;
-    }
-    th_ctx = th_was;
-    vd_views.assign(views, views + n_views);
-    vd_open = true;
+    const Session kind = views ? Session::ViewsAdapt : Session::Adapt;
+    gs_status s = admit(Call::Begin, kind);
+    if (s != GS_OK) return s;
+    if (views && (s = views_form_check()) != GS_OK) return s;
+    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
+    if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
+    if ((s = adapt_settings_check(ss)) != GS_OK) return s;
+    const uint64_t R = (uint64_t)ss->max_samples / ss->batch_size + 1u;
+    DeviceGuard guard;
+    // (views: the batch's own tile height, so that no tile straddles two views)
+    const int32_t ath = views ? gs_views_tile_h(views[0].cam.image_height, th) : th;
+    if ((s = partition(cam, seed, nullptr, views != nullptr, ath)) != GS_OK) return s;
+    if (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll) return fail(GS_ERR_ARG, "bad partition");
+    if ((s = adapt_alloc(gs_round_layout((uint64_t)cap, R))) != GS_OK) return close_session(), s;
+    ad.cam = *cam;
+    ad.ss = *ss;
+    ad.th = ath;
+    ad.seed = seed;
+    ad.R = (uint32_t)R;
+    ad.active = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
+    if (views) ad.views.assign(views, views + n_views);
+    open = kind;
     return GS_OK;
 }
 
-gs_status gs_multi::adapt_open(const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed, bool round_robin) {
-    if (vd_open) return fail(GS_ERR_ARG, "a views adaptation is open: gs_multi_views_adapt_end first");
-    if (ad_open) return fail(GS_ERR_ARG, "an adaptation is already open: gs_multi_adapt_end first");
-    if (acc_open) return fail(GS_ERR_ARG, "an accumulation is open: gs_multi_accum_end first");
-    if (va_open) return fail(GS_ERR_ARG, "a views accumulation is open: gs_multi_views_accum_end first");
-    if (comms_broken) return fail(GS_ERR_HIP, "the context's communicator was aborted after a failed collective");
-    if (cam->image_width <= 0 || cam->image_height <= 0) return fail(GS_ERR_ARG, "bad image size");
-    gs_status s = adapt_settings_check(ss);
-    if (s != GS_OK) return s;
-    const uint64_t R = (uint64_t)ss->max_samples / ss->batch_size + 1u;
-    DeviceGuard guard;
-    double plan_ms = 0.0;
-    s = partition(cam, seed, &plan_ms, round_robin);
-    if (s != GS_OK) return s;
-    if (cap <= 0 || cap >= (int64_t)0xFFFFFFFFll) return fail(GS_ERR_ARG, "bad partition");
-    const GsRoundLayout l = gs_round_layout((uint64_t)cap, R);
+gs_status gs_multi::adapt_alloc(const GsRoundLayout& l) {
     for (auto& d : dev) {
         HIPOK(hipSetDevice(d.id));
-        GROW(d.rstate, l.bytes);
-        GROW(d.map_samples, cap * 4);
-        GROW(d.map_error, cap * 4);
-        HIPOK(hipMemsetAsync(d.rstate.p, 0, l.bytes, d.stream));
-        HIPOK(hipMemsetAsync(d.map_samples.p, 0, (size_t)cap * 4, d.stream));
-        HIPOK(hipMemsetAsync(d.map_error.p, 0, (size_t)cap * 4, d.stream));
-        if (!d.h_summary &&
-            hipHostMalloc((void**)&d.h_summary, kRoundSummaryWords * 8, hipHostMallocDefault) != hipSuccess)
+        GROW(d.ad.rstate, l.bytes);
+        GROW(d.ad.map_samples, cap * 4);
+        GROW(d.ad.map_error, cap * 4);
+        HIPOK(hipMemsetAsync(d.ad.rstate.p, 0, l.bytes, d.stream));
+        HIPOK(hipMemsetAsync(d.ad.map_samples.p, 0, (size_t)cap * 4, d.stream));
+        HIPOK(hipMemsetAsync(d.ad.map_error.p, 0, (size_t)cap * 4, d.stream));
+        if (!d.ad.h_summary &&
+            hipHostMalloc((void**)&d.ad.h_summary, kRoundSummaryWords * 8, hipHostMallocDefault) != hipSuccess)
             return fail(GS_ERR_OOM, "hipHostMalloc of the round summary failed");
         HIPOK(hipStreamSynchronize(d.stream));
     }
-    ad_cam = *cam;
-    ad_ss = *ss;
-    ad_seed = seed;
-    ad_R = (uint32_t)R;
-    ad_rounds = 0;
-    ad_active = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
-    ad_samples_total = ad_samples_max = 0;
-    ad_counters = ad_base = ad_dev = gs_counters{};
-    ad_fresh = true;
-    ad_open = true;
     return GS_OK;
-}
-
-void gs_multi::adapt_end() {
-    DeviceGuard guard;
-    for (auto& d : dev) {
-        (void)hipSetDevice(d.id);
-        if (d.stream && !comms_broken) (void)hipStreamSynchronize(d.stream);
-        d.rstate.release();
-        d.map_samples.release();
-        d.map_error.release();
-    }
-    if (vd_open) {  // (the context's own tile height again)
-        th = th_ctx;
-        part_ready = false;
-        vd_open = false;
-    }
-    ad_open = false;
 }
 
 gs_status gs_multi::adapt_pass(uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats) {
     if (rounds == 0) return fail(GS_ERR_ARG, "a pass of 0 rounds");
-    const uint32_t todo = adapt_finished() ? 0u : std::min(rounds, ad_R - ad_rounds);
-    if (!vd_open) return render(&ad_cam, &ad_ss, ad_seed, out, stats, 0, true, todo);
-    if (out && out->ppm_text) return fail(GS_ERR_ARG, "a views pass writes no PPM text");
-    const ViewsCall vw{vd_views.data(), (uint32_t)vd_views.size(), 0};
-    return render(&ad_cam, &ad_ss, 0, out, stats, 0, true, todo, &vw);
+    if (open == Session::ViewsAdapt && out && out->ppm_text) return fail(GS_ERR_ARG, "a views pass writes no PPM text");
+    Frame f{open, &ad.cam, &ad.ss, ad.seed, ad.th};
+    f.views = ad.views.empty() ? nullptr : ad.views.data();
+    f.n_views = (uint32_t)ad.views.size();
+    f.rounds = ad.finished() ? 0u : std::min(rounds, ad.R - ad.rounds);
+    return render(f, out, stats);
 }
 
 gs_status gs_multi::adapt_maps(uint32_t* samples, float* rel_error) {
@@ -927,12 +978,12 @@ gs_status gs_multi::adapt_maps(uint32_t* samples, float* rel_error) {
         HIPOK(hipSetDevice(d.id));
         HIPOK(hipStreamSynchronize(d.stream));
         if (samples) {
-            HIPOK(hipMemcpy(packed.data(), d.map_samples.p, packed.size(), hipMemcpyDeviceToHost));
-            permute_rank(i, ad_cam, (uint8_t*)samples, packed.data(), 4, true);
+            HIPOK(hipMemcpy(packed.data(), d.ad.map_samples.p, packed.size(), hipMemcpyDeviceToHost));
+            permute_rank(i, ad.cam, (uint8_t*)samples, packed.data(), 4, true);
         }
         if (rel_error) {
-            HIPOK(hipMemcpy(packed.data(), d.map_error.p, packed.size(), hipMemcpyDeviceToHost));
-            permute_rank(i, ad_cam, (uint8_t*)rel_error, packed.data(), 4, true);
+            HIPOK(hipMemcpy(packed.data(), d.ad.map_error.p, packed.size(), hipMemcpyDeviceToHost));
+            permute_rank(i, ad.cam, (uint8_t*)rel_error, packed.data(), 4, true);
         }
     }
     return GS_OK;
@@ -943,32 +994,28 @@ gs_status gs_multi::adapt_download(double* sums, uint32_t* state) {
     std::vector<uint8_t> packed((size_t)cap * 40);
     for (int i = 0; i < (int)dev.size(); i++) {
         Device& d = dev[i];
-        const size_t rc = (size_t)rank_cap(i, ad_cam);
-        const GsRoundLayout l = gs_round_layout(rc, ad_R);
+        const size_t rc = (size_t)rank_cap(i, ad.cam);
+        const GsRoundLayout l = gs_round_layout(rc, ad.R);
         if (rc == 0) continue;
         HIPOK(hipSetDevice(d.id));
         HIPOK(hipStreamSynchronize(d.stream));
         if (sums) {
-            HIPOK(hipMemcpy(packed.data(), (const char*)d.rstate.p + l.pstate, rc * 40, hipMemcpyDeviceToHost));
-            permute_rank(i, ad_cam, (uint8_t*)sums, packed.data(), 40, true);
+            HIPOK(hipMemcpy(packed.data(), (const char*)d.ad.rstate.p + l.pstate, rc * 40, hipMemcpyDeviceToHost));
+            permute_rank(i, ad.cam, (uint8_t*)sums, packed.data(), 40, true);
         }
-        HIPOK(hipMemcpy(packed.data(), (const char*)d.rstate.p + l.batches, rc * 4, hipMemcpyDeviceToHost));
-        permute_rank(i, ad_cam, (uint8_t*)state, packed.data(), 4, true);
+        HIPOK(hipMemcpy(packed.data(), (const char*)d.ad.rstate.p + l.batches, rc * 4, hipMemcpyDeviceToHost));
+        permute_rank(i, ad.cam, (uint8_t*)state, packed.data(), 4, true);
     }
     return GS_OK;
 }
 
-// Behind adapt_begin: the state of a checkpoint into the ranks' blobs (closes the adaptation again
-// when it cannot).
+// Behind adapt_begin: a checkpoint's state into the ranks' blobs (closes the adaptation when it cannot).
 gs_status gs_multi::adapt_fill(uint32_t rounds_done, const double* sums, const uint32_t* state,
                                const gs_counters* counters) {
-    const gs_camera* cam = &ad_cam;
-    const gs_sample_settings* ss = &ad_ss;
-    auto bail = [&](gs_status st) {
-        adapt_end();
-        return st;
-    };
-    if (rounds_done > ad_R) return bail(fail(GS_ERR_ARG, "rounds_done exceeds the settings' rounds"));
+    const gs_camera* cam = &ad.cam;
+    const uint64_t batch = ad.ss.batch_size;
+    auto bail = [&](gs_status st) { return close_session(), st; };
+    if (rounds_done > ad.R) return bail(fail(GS_ERR_ARG, "rounds_done exceeds the settings' rounds"));
     // every pixel's word against rounds_done: an active pixel has taken every round so far, a
     // stopped one at least one and no more than that
     const uint64_t npx = (uint64_t)cam->image_width * (uint64_t)cam->image_height;
@@ -976,14 +1023,14 @@ gs_status gs_multi::adapt_fill(uint32_t rounds_done, const double* sums, const u
     for (uint64_t k = 0; k < npx; k++) {
         const uint32_t nb = state[k] & ~GS_ADAPT_STOPPED;
         const bool stopped = (state[k] & GS_ADAPT_STOPPED) != 0;
-        if (stopped ? (nb < 1 || nb > rounds_done) : (nb != rounds_done || (rounds_done == ad_R && rounds_done)))
+        if (stopped ? (nb < 1 || nb > rounds_done) : (nb != rounds_done || (rounds_done == ad.R && rounds_done)))
             return bail(fail(GS_ERR_ARG, "a pixel's state disagrees with rounds_done"));
         active += stopped ? 0u : 1u;
-        total += (uint64_t)nb * ss->batch_size;
-        most = std::max<uint64_t>(most, (uint64_t)nb * ss->batch_size);
+        total += nb * batch;
+        most = std::max(most, nb * batch);
     }
     if (rounds_done == 0) {  // (nothing to fill: the first pass initialises the state)
-        ad_counters = ad_base = *counters;
+        ad.counters = ad.base = *counters;
         return GS_OK;
     }
     DeviceGuard guard;
@@ -992,7 +1039,7 @@ gs_status gs_multi::adapt_fill(uint32_t rounds_done, const double* sums, const u
     for (int i = 0; i < (int)dev.size(); i++) {
         Device& d = dev[i];
         const size_t cap = (size_t)rank_cap(i, *cam);  // (the rank's own: its launches lay the state out for it)
-        const GsRoundLayout l = gs_round_layout(cap, ad_R);
+        const GsRoundLayout l = gs_round_layout(cap, ad.R);
         if (cap == 0) continue;
         std::fill(psums.begin(), psums.end(), 0.0);
         std::fill(words.begin(), words.end(), GS_ADAPT_STOPPED);  // (padding: never active)
@@ -1005,7 +1052,7 @@ gs_status gs_multi::adapt_fill(uint32_t rounds_done, const double* sums, const u
             if (words[k] == GS_ADAPT_STOPPED) words[k] = 0u;
         }
         const uint32_t n_act = (uint32_t)list.size();
-        char* blob = (char*)d.rstate.p;
+        char* blob = (char*)d.ad.rstate.p;
         if (hipSetDevice(d.id) != hipSuccess ||
             hipMemcpy(blob + l.pstate, psums.data(), cap * 40, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(blob + l.batches, words.data(), cap * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -1014,41 +1061,187 @@ gs_status gs_multi::adapt_fill(uint32_t rounds_done, const double* sums, const u
             hipMemcpy(blob + l.counts + (size_t)rounds_done * 4, &n_act, 4, hipMemcpyHostToDevice) != hipSuccess)
             return bail(fail(GS_ERR_HIP, "uploading the round state failed"));
     }
-    ad_rounds = rounds_done;
-    ad_active = active;
-    ad_samples_total = total;
-    ad_samples_max = most;
-    ad_counters = ad_base = *counters;
+    ad.rounds = rounds_done;
+    ad.active = active;
+    ad.samples_total = total;
+    ad.samples_max = most;
+    ad.counters = ad.base = *counters;
     return GS_OK;
 }
 
-void gs_multi::permute_rank(int rank, const gs_camera& cam, uint8_t* image, uint8_t* packed, size_t elem,
-                            bool to_image) const {
-    const int64_t W = cam.image_width, H = cam.image_height, tpx = (int64_t)tw * th;
-    const int64_t tx = (W + tw - 1) / tw, nt = tx * ((H + th - 1) / th);
-    int64_t ns = cap / tpx;
-    if (order.empty()) {
-        gs_partition p{rank, (int32_t)dev.size(), tw, th, nullptr, 0, 0};
-        ns = std::min<int64_t>(ns, gs_partition_capacity(&cam, &p) / tpx);
-    }
-    for (int64_t sl = 0; sl < ns; sl++) {
-        const int64_t tile = slot_tile(rank, sl);
-        if (tile < 0 || tile >= nt) continue;
-        const int64_t x0 = (tile % tx) * tw, y0 = (tile / tx) * th;
-        const int64_t nx = std::min<int64_t>(tw, W - x0);
-        for (int64_t y = 0; y < th && y0 + y < H; y++) {
-            uint8_t* img = image + (size_t)((y0 + y) * W + x0) * elem;
-            uint8_t* pk = packed + (size_t)(sl * tpx + y * tw) * elem;
-            if (to_image)
-                std::memcpy(img, pk, (size_t)nx * elem);
-            else
-                std::memcpy(pk, img, (size_t)nx * elem);
-        }
-    }
+namespace {
+
+// A session's own call: the context, its lock, the session open, then the call itself.
+template <class M, class F>
+gs_status in_session(M* m, Session s, Call call, F body) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    const gs_status st = m->admit(call, s);
+    return st != GS_OK ? st : body();
 }
+
+// What gs_adapt_info and gs_views_adapt_info share.
+template <class Info>
+void adapt_info_fill(const AdaptState& a, Info* info) {
+    std::memset(info, 0, sizeof(*info));
+    info->width = a.cam.image_width;
+    info->batch = a.ss.batch_size;
+    info->rounds = a.rounds;
+    info->max_rounds = a.R;
+    info->finished = a.finished() ? 1u : 0u;
+    info->active_pixels = a.active;
+    info->samples_total = a.samples_total;
+    info->samples_max = a.samples_max;
+    info->counters = a.counters;
+}
+
+}  // namespace
 
 extern "C" {
 
+// ---- progressive accumulation
+gs_status gs_multi_accum_begin(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk) {
+    if (!m || !cam) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    return m->accum_begin(cam, seed, chunk);
+}
+
+gs_status gs_multi_accum_pass(gs_multi* m, uint32_t samples, const gs_multi_outputs* out, gs_stats* stats) {
+    return in_session(m, Session::Accum, Call::Pass, [&]() -> gs_status {
+        const uint32_t c = m->acc.chunk;
+        if (samples == 0 || samples % c != 0 || samples / c > 64u)
+            return fail(GS_ERR_ARG, "a pass is 1 to 64 whole chunks of samples");
+        if (m->acc.samples + samples > 0xFFFFFFFFull) return fail(GS_ERR_ARG, "the frame's samples overflow 32 bits");
+        const gs_sample_settings ss{0.0, 0.0, samples, 0};
+        return m->render(Frame{Session::Accum, &m->acc.cam, &ss, m->acc.seed, m->th}, out, stats);
+    });
+}
+
+gs_status gs_multi_accum_info(const gs_multi* m, gs_accum_info* info) {
+    if (!m || !info) return fail(GS_ERR_ARG, "null argument");
+    return in_session(m, Session::Accum, Call::Other, [&]() -> gs_status {
+        std::memset(info, 0, sizeof(*info));
+        info->width = m->acc.cam.image_width;
+        info->height = m->acc.cam.image_height;
+        info->chunk = m->acc.chunk;
+        info->passes = m->acc.passes;
+        info->seed = m->acc.seed;
+        info->samples = m->acc.samples;
+        info->last_delta = m->acc.last_delta;
+        info->counters = m->acc.counters;
+        return GS_OK;
+    });
+}
+
+gs_status gs_multi_accum_download(gs_multi* m, double* sums) {
+    if (!m || !sums) return fail(GS_ERR_ARG, "null argument");
+    return in_session(m, Session::Accum, Call::Other, [&] { return m->permute_sums(m->acc.cam, sums, true); });
+}
+
+gs_status gs_multi_accum_upload(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk, uint64_t samples,
+                                const double* sums, const gs_counters* counters) {
+    if (!m || !cam || !sums || !counters) return fail(GS_ERR_ARG, "null argument");
+    const uint32_t c = chunk ? chunk : 16u;
+    if (samples % c != 0 || samples > 0xFFFFFFFFull)
+        return fail(GS_ERR_ARG, "a checkpoint's samples are whole chunks, below 2^32");
+    std::lock_guard<std::mutex> lock(m->mu);
+    gs_status s = m->accum_begin(cam, seed, chunk);
+    if (s != GS_OK) return s;
+    s = m->permute_sums(m->acc.cam, const_cast<double*>(sums), false);
+    if (s != GS_OK) return m->close_session(), s;
+    m->acc.samples = samples;
+    m->acc.counters = *counters;
+    return GS_OK;
+}
+
+gs_status gs_multi_accum_end(gs_multi* m) {
+    return in_session(m, Session::Accum, Call::Other, [&] { return m->close_session(), GS_OK; });
+}
+
+// ---- progressive views
+gs_status gs_multi_views_accum_begin(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk) {
+    if (!m) return fail(GS_ERR_ARG, "null context");
+    std::lock_guard<std::mutex> lock(m->mu);
+    const uint32_t c = chunk ? chunk : 16u;
+    gs_camera tall;
+    gs_status s = gs_views_check(m->dev[0].scene, views, n_views, c, c, &tall);  // (one chunk: the views' own rules)
+    if (s != GS_OK) return s;
+    return m->views_accum_begin(tall, views, n_views, chunk);
+}
+
+gs_status gs_multi_views_accum_pass(gs_multi* m, uint32_t samples, const uint8_t* selected, const gs_multi_outputs* out,
+                                    gs_stats* stats) {
+    return in_session(m, Session::ViewsAccum, Call::Pass, [&]() -> gs_status {
+        const ViewsAccumState& va = m->va;
+        if (out && out->ppm_text) return fail(GS_ERR_ARG, "a views pass writes no PPM text");
+        const uint32_t c = va.chunk, nv = (uint32_t)va.views.size();
+        if (samples == 0 || samples % c != 0 || samples / c > 64u)
+            return fail(GS_ERR_ARG, "a pass is 1 to 64 whole chunks of samples");
+        Frame f{Session::ViewsAccum, &va.tall, nullptr, 0, va.th};
+        f.views = va.views.data();
+        f.n_views = nv;
+        f.chunk = c;
+        f.selected = selected;
+        gs_status s = gs_views_pass_check(nv, va.samples.data(), selected, samples, c, &f.base);
+        if (s != GS_OK) return s;
+        // (rank 0 holds the most tiles of the round-robin cut: its share bounds every rank's)
+        s = gs_views_check_cap(m->rank_cap(0, va.tall), samples, c);
+        if (s != GS_OK) return s;
+        const gs_sample_settings ss{0.0, 0.0, samples, 0};
+        f.ss = &ss;
+        return m->render(f, out, stats);
+    });
+}
+
+gs_status gs_multi_views_accum_info(const gs_multi* m, gs_views_accum_info* info, uint32_t* view_samples_out,
+                                    double* delta_out) {
+    if (!m || !info) return fail(GS_ERR_ARG, "null argument");
+    return in_session(m, Session::ViewsAccum, Call::Other, [&]() -> gs_status {
+        const ViewsAccumState& va = m->va;
+        std::memset(info, 0, sizeof(*info));
+        info->width = va.views[0].cam.image_width;
+        info->height = va.views[0].cam.image_height;
+        info->n_views = (uint32_t)va.views.size();
+        info->chunk = va.chunk;
+        info->passes = va.passes;
+        info->tile_h = va.th;
+        info->counters = va.counters;
+        if (view_samples_out) std::memcpy(view_samples_out, va.samples.data(), va.samples.size() * sizeof(uint32_t));
+        if (delta_out) std::memcpy(delta_out, va.delta.data(), va.delta.size() * sizeof(double));
+        return GS_OK;
+    });
+}
+
+gs_status gs_multi_views_accum_download(gs_multi* m, double* sums) {
+    if (!m || !sums) return fail(GS_ERR_ARG, "null argument");
+    return in_session(m, Session::ViewsAccum, Call::Other, [&] { return m->permute_sums(m->va.tall, sums, true); });
+}
+
+gs_status gs_multi_views_accum_upload(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk,
+                                      const uint32_t* view_samples, const double* sums, const gs_counters* counters) {
+    if (!m || !view_samples || !sums || !counters) return fail(GS_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lock(m->mu);
+    const uint32_t c = chunk ? chunk : 16u;
+    gs_camera tall;
+    gs_status s = gs_views_check(m->dev[0].scene, views, n_views, c, c, &tall);
+    if (s != GS_OK) return s;
+    for (uint32_t v = 0; v < n_views; v++)
+        if (view_samples[v] % c != 0)
+            return fail(GS_ERR_ARG, "a checkpoint's samples are whole chunks (view " + std::to_string(v) + ")");
+    s = m->views_accum_begin(tall, views, n_views, chunk);
+    if (s != GS_OK) return s;
+    s = m->permute_sums(m->va.tall, const_cast<double*>(sums), false);
+    if (s != GS_OK) return m->close_session(), s;
+    m->va.samples.assign(view_samples, view_samples + n_views);
+    m->va.counters = *counters;
+    return GS_OK;
+}
+
+gs_status gs_multi_views_accum_end(gs_multi* m) {
+    return in_session(m, Session::ViewsAccum, Call::Other, [&] { return m->close_session(), GS_OK; });
+}
+
+// ---- progressive adaptation
 gs_status gs_multi_adapt_begin(gs_multi* m, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed) {
     if (!m || !cam || !ss) return fail(GS_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> lock(m->mu);
@@ -1056,43 +1249,26 @@ gs_status gs_multi_adapt_begin(gs_multi* m, const gs_camera* cam, const gs_sampl
 }
 
 gs_status gs_multi_adapt_pass(gs_multi* m, uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open: gs_multi_adapt_begin first");
-    return m->adapt_pass(rounds, out, stats);
+    return in_session(m, Session::Adapt, Call::Pass, [&] { return m->adapt_pass(rounds, out, stats); });
 }
 
 gs_status gs_multi_adapt_info(const gs_multi* m, gs_adapt_info* info) {
     if (!m || !info) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open");
-    std::memset(info, 0, sizeof(*info));
-    info->width = m->ad_cam.image_width;
-    info->height = m->ad_cam.image_height;
-    info->batch = m->ad_ss.batch_size;
-    info->rounds = m->ad_rounds;
-    info->max_rounds = m->ad_R;
-    info->finished = m->adapt_finished() ? 1u : 0u;
-    info->seed = m->ad_seed;
-    info->active_pixels = m->ad_active;
-    info->samples_total = m->ad_samples_total;
-    info->samples_max = m->ad_samples_max;
-    info->counters = m->ad_counters;
-    return GS_OK;
+    return in_session(m, Session::Adapt, Call::Other, [&]() -> gs_status {
+        adapt_info_fill(m->ad, info);
+        info->height = m->ad.cam.image_height;
+        info->seed = m->ad.seed;
+        return GS_OK;
+    });
 }
 
 gs_status gs_multi_adapt_maps(gs_multi* m, uint32_t* samples, float* rel_error) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open");
-    return m->adapt_maps(samples, rel_error);
+    return in_session(m, Session::Adapt, Call::Other, [&] { return m->adapt_maps(samples, rel_error); });
 }
 
 gs_status gs_multi_adapt_download(gs_multi* m, double* sums, uint32_t* state) {
     if (!m || !sums || !state) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open");
-    return m->adapt_download(sums, state);
+    return in_session(m, Session::Adapt, Call::Other, [&] { return m->adapt_download(sums, state); });
 }
 
 gs_status gs_multi_adapt_upload(gs_multi* m, const gs_camera* cam, const gs_sample_settings* ss, uint64_t seed,
@@ -1106,11 +1282,7 @@ gs_status gs_multi_adapt_upload(gs_multi* m, const gs_camera* cam, const gs_samp
 }
 
 gs_status gs_multi_adapt_end(gs_multi* m) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->ad_open || m->vd_open) return fail(GS_ERR_ARG, "no adaptation is open");
-    m->adapt_end();
-    return GS_OK;
+    return in_session(m, Session::Adapt, Call::Other, [&] { return m->close_session(), GS_OK; });
 }
 
 // ---- adaptive views: the adaptation's calls on the tall frame
@@ -1133,60 +1305,43 @@ gs_status gs_multi_views_adapt_begin(gs_multi* m, const gs_view* views, uint32_t
 }
 
 gs_status gs_multi_views_adapt_pass(gs_multi* m, uint32_t rounds, const gs_multi_outputs* out, gs_stats* stats) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open: gs_multi_views_adapt_begin first");
-    return m->adapt_pass(rounds, out, stats);
+    return in_session(m, Session::ViewsAdapt, Call::Pass, [&] { return m->adapt_pass(rounds, out, stats); });
 }
 
 gs_status gs_multi_views_adapt_info(gs_multi* m, gs_views_adapt_info* info, uint64_t* view_active_out) {
     if (!m || !info) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open");
-    const uint32_t nv = (uint32_t)m->vd_views.size();
-    std::memset(info, 0, sizeof(*info));
-    info->width = m->ad_cam.image_width;
-    info->height = m->vd_views[0].cam.image_height;
-    info->n_views = nv;
-    info->tile_h = m->th;
-    info->batch = m->ad_ss.batch_size;
-    info->rounds = m->ad_rounds;
-    info->max_rounds = m->ad_R;
-    info->finished = m->adapt_finished() ? 1u : 0u;
-    info->active_pixels = m->ad_active;
-    info->samples_total = m->ad_samples_total;
-    info->samples_max = m->ad_samples_max;
-    info->counters = m->ad_counters;
-    if (view_active_out) {  // (not hot: the state words cross to the host)
-        const size_t vpx = (size_t)info->width * (size_t)info->height;
-        if (m->ad_rounds == 0) {
-            for (uint32_t v = 0; v < nv; v++) view_active_out[v] = vpx;
-            return GS_OK;
+    return in_session(m, Session::ViewsAdapt, Call::Other, [&]() -> gs_status {
+        const uint32_t nv = (uint32_t)m->ad.views.size();
+        adapt_info_fill(m->ad, info);
+        info->height = m->ad.views[0].cam.image_height;
+        info->n_views = nv;
+        info->tile_h = m->ad.th;
+        if (view_active_out) {  // (not hot: the state words cross to the host)
+            const size_t vpx = (size_t)info->width * (size_t)info->height;
+            if (m->ad.rounds == 0) {
+                for (uint32_t v = 0; v < nv; v++) view_active_out[v] = vpx;
+                return GS_OK;
+            }
+            std::vector<uint32_t> state(vpx * nv);
+            const gs_status s = m->adapt_download(nullptr, state.data());
+            if (s != GS_OK) return s;
+            for (uint32_t v = 0; v < nv; v++) {
+                uint64_t act = 0;
+                for (size_t k = 0; k < vpx; k++) act += (state[v * vpx + k] & GS_ADAPT_STOPPED) ? 0u : 1u;
+                view_active_out[v] = act;
+            }
         }
-        std::vector<uint32_t> state(vpx * nv);
-        const gs_status s = m->adapt_download(nullptr, state.data());
-        if (s != GS_OK) return s;
-        for (uint32_t v = 0; v < nv; v++) {
-            uint64_t act = 0;
-            for (size_t k = 0; k < vpx; k++) act += (state[v * vpx + k] & GS_ADAPT_STOPPED) ? 0u : 1u;
-            view_active_out[v] = act;
-        }
-    }
-    return GS_OK;
+        return GS_OK;
+    });
 }
 
 gs_status gs_multi_views_adapt_maps(gs_multi* m, uint32_t* samples, float* rel_error) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open");
-    return m->adapt_maps(samples, rel_error);
+    return in_session(m, Session::ViewsAdapt, Call::Other, [&] { return m->adapt_maps(samples, rel_error); });
 }
 
 gs_status gs_multi_views_adapt_download(gs_multi* m, double* sums, uint32_t* state) {
     if (!m || !sums || !state) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open");
-    return m->adapt_download(sums, state);
+    return in_session(m, Session::ViewsAdapt, Call::Other, [&] { return m->adapt_download(sums, state); });
 }
 
 gs_status gs_multi_views_adapt_upload(gs_multi* m, const gs_view* views, uint32_t n_views, const gs_sample_settings* ss,
@@ -1202,79 +1357,7 @@ gs_status gs_multi_views_adapt_upload(gs_multi* m, const gs_view* views, uint32_
 }
 
 gs_status gs_multi_views_adapt_end(gs_multi* m) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->vd_open) return fail(GS_ERR_ARG, "no views adaptation is open");
-    m->adapt_end();
-    return GS_OK;
-}
-
-gs_status gs_multi_accum_begin(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk) {
-    if (!m || !cam) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    return m->accum_begin(cam, seed, chunk);
-}
-
-gs_status gs_multi_accum_pass(gs_multi* m, uint32_t samples, const gs_multi_outputs* out, gs_stats* stats) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->acc_open) return fail(GS_ERR_ARG, "no accumulation is open: gs_multi_accum_begin first");
-    const uint32_t c = m->acc_chunk;
-    if (samples == 0 || samples % c != 0 || samples / c > 64u)
-        return fail(GS_ERR_ARG, "a pass is 1 to 64 whole chunks of samples");
-    if (m->acc_samples + samples > 0xFFFFFFFFull) return fail(GS_ERR_ARG, "the frame's samples overflow 32 bits");
-    const gs_sample_settings ss{0.0, 0.0, samples, 0};
-    return m->render(&m->acc_cam, &ss, m->acc_seed, out, stats, samples);
-}
-
-gs_status gs_multi_accum_info(const gs_multi* m, gs_accum_info* info) {
-    if (!m || !info) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->acc_open) return fail(GS_ERR_ARG, "no accumulation is open");
-    std::memset(info, 0, sizeof(*info));
-    info->width = m->acc_cam.image_width;
-    info->height = m->acc_cam.image_height;
-    info->chunk = m->acc_chunk;
-    info->passes = m->acc_passes;
-    info->seed = m->acc_seed;
-    info->samples = m->acc_samples;
-    info->last_delta = m->acc_last_delta;
-    info->counters = m->acc_counters;
-    return GS_OK;
-}
-
-gs_status gs_multi_accum_download(gs_multi* m, double* sums) {
-    if (!m || !sums) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->acc_open) return fail(GS_ERR_ARG, "no accumulation is open");
-    return m->permute_sums(sums, true);
-}
-
-gs_status gs_multi_accum_upload(gs_multi* m, const gs_camera* cam, uint64_t seed, uint32_t chunk, uint64_t samples,
-                                const double* sums, const gs_counters* counters) {
-    if (!m || !cam || !sums || !counters) return fail(GS_ERR_ARG, "null argument");
-    const uint32_t c = chunk ? chunk : 16u;
-    if (samples % c != 0 || samples > 0xFFFFFFFFull)
-        return fail(GS_ERR_ARG, "a checkpoint's samples are whole chunks, below 2^32");
-    std::lock_guard<std::mutex> lock(m->mu);
-    gs_status s = m->accum_begin(cam, seed, chunk);
-    if (s != GS_OK) return s;
-    s = m->permute_sums(const_cast<double*>(sums), false);
-    if (s != GS_OK) {
-        m->accum_end();
-        return s;
-    }
-    m->acc_samples = samples;
-    m->acc_counters = *counters;
-    return GS_OK;
-}
-
-gs_status gs_multi_accum_end(gs_multi* m) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->acc_open) return fail(GS_ERR_ARG, "no accumulation is open");
-    m->accum_end();
-    return GS_OK;
+    return in_session(m, Session::ViewsAdapt, Call::Other, [&] { return m->close_session(), GS_OK; });
 }
 
 const char* gs_rccl_library(void) {
@@ -1344,7 +1427,7 @@ gs_status gs_multi_render(gs_multi* m, const gs_camera* cam, const gs_sample_set
                           const gs_multi_outputs* out, gs_stats* stats) {
     if (!m) return fail(GS_ERR_ARG, "null context");
     std::lock_guard<std::mutex> lock(m->mu);
-    return m->render(cam, ss, seed, out, stats);
+    return m->render(Frame{Session::None, cam, ss, seed, m->th}, out, stats);
 }
 
 gs_status gs_multi_render_views(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t samples, uint32_t chunk,
@@ -1361,97 +1444,11 @@ gs_status gs_multi_render_views(gs_multi* m, const gs_view* views, uint32_t n_vi
     s = gs_views_check_cap(gs_partition_capacity(&tall, &p0), samples, c);
     if (s != GS_OK) return s;
     const gs_sample_settings ss{0.0, 0.0, samples, 0};
-    const gs_multi::ViewsCall vw{views, n_views, c};
-    return m->render(&tall, &ss, 0, out, stats, 0, false, 0, &vw);
-}
-
-// ---- progressive views
-gs_status gs_multi_views_accum_begin(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    const uint32_t c = chunk ? chunk : 16u;
-    gs_camera tall;
-    gs_status s = gs_views_check(m->dev[0].scene, views, n_views, c, c, &tall);  // (one chunk: the views' own rules)
-    if (s != GS_OK) return s;
-    return m->views_accum_begin(views, n_views, chunk);
-}
-
-gs_status gs_multi_views_accum_pass(gs_multi* m, uint32_t samples, const uint8_t* selected, const gs_multi_outputs* out,
-                                    gs_stats* stats) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->va_open) return fail(GS_ERR_ARG, "no views accumulation is open: gs_multi_views_accum_begin first");
-    if (out && out->ppm_text) return fail(GS_ERR_ARG, "a views pass writes no PPM text");
-    const uint32_t c = m->va_chunk, nv = (uint32_t)m->va_views.size();
-    if (samples == 0 || samples % c != 0 || samples / c > 64u)
-        return fail(GS_ERR_ARG, "a pass is 1 to 64 whole chunks of samples");
-    uint32_t base = 0;
-    gs_status s = gs_views_pass_check(nv, m->va_samples.data(), selected, samples, c, &base);
-    if (s != GS_OK) return s;
-    // (rank 0 holds the most tiles of the round-robin cut: its share bounds every rank's)
-    const gs_partition p0{0, (int32_t)m->dev.size(), m->tw, m->th, nullptr, 0, 0};
-    s = gs_views_check_cap(gs_partition_capacity(&m->va_tall, &p0), samples, c);
-    if (s != GS_OK) return s;
-    const gs_sample_settings ss{0.0, 0.0, samples, 0};
-    const gs_multi::ViewsCall vw{m->va_views.data(), nv, c};
-    const gs_multi::ViewsPass vp{selected, base};
-    return m->render(&m->va_tall, &ss, 0, out, stats, 0, false, 0, &vw, &vp);
-}
-
-gs_status gs_multi_views_accum_info(const gs_multi* m, gs_views_accum_info* info, uint32_t* view_samples_out,
-                                    double* delta_out) {
-    if (!m || !info) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->va_open) return fail(GS_ERR_ARG, "no views accumulation is open");
-    std::memset(info, 0, sizeof(*info));
-    info->width = m->va_views[0].cam.image_width;
-    info->height = m->va_views[0].cam.image_height;
-    info->n_views = (uint32_t)m->va_views.size();
-    info->chunk = m->va_chunk;
-    info->passes = m->va_passes;
-    info->tile_h = m->th;
-    info->counters = m->va_counters;
-    if (view_samples_out) std::memcpy(view_samples_out, m->va_samples.data(), m->va_samples.size() * sizeof(uint32_t));
-    if (delta_out) std::memcpy(delta_out, m->va_delta.data(), m->va_delta.size() * sizeof(double));
-    return GS_OK;
-}
-
-gs_status gs_multi_views_accum_download(gs_multi* m, double* sums) {
-    if (!m || !sums) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->va_open) return fail(GS_ERR_ARG, "no views accumulation is open");
-    return m->permute_sums(sums, true);
-}
-
-gs_status gs_multi_views_accum_upload(gs_multi* m, const gs_view* views, uint32_t n_views, uint32_t chunk,
-                                      const uint32_t* view_samples, const double* sums, const gs_counters* counters) {
-    if (!m || !view_samples || !sums || !counters) return fail(GS_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> lock(m->mu);
-    const uint32_t c = chunk ? chunk : 16u;
-    gs_camera tall;
-    gs_status s = gs_views_check(m->dev[0].scene, views, n_views, c, c, &tall);
-    if (s != GS_OK) return s;
-    for (uint32_t v = 0; v < n_views; v++)
-        if (view_samples[v] % c != 0)
-            return fail(GS_ERR_ARG, "a checkpoint's samples are whole chunks (view " + std::to_string(v) + ")");
-    s = m->views_accum_begin(views, n_views, chunk);
-    if (s != GS_OK) return s;
-    s = m->permute_sums(const_cast<double*>(sums), false);
-    if (s != GS_OK) {
-        m->views_accum_end();
-        return s;
-    }
-    m->va_samples.assign(view_samples, view_samples + n_views);
-    m->va_counters = *counters;
-    return GS_OK;
-}
-
-gs_status gs_multi_views_accum_end(gs_multi* m) {
-    if (!m) return fail(GS_ERR_ARG, "null context");
-    std::lock_guard<std::mutex> lock(m->mu);
-    if (!m->va_open) return fail(GS_ERR_ARG, "no views accumulation is open");
-    m->views_accum_end();
-    return GS_OK;
+    Frame f{Session::None, &tall, &ss, 0, m->th};
+    f.views = views;
+    f.n_views = n_views;
+    f.chunk = c;
+    return m->render(f, out, stats);
 }
 
 gs_status gs_multi_frame(const gs_multi* m, const float** d_rgb, const uint8_t** d_rgb8, int32_t* device) {
@@ -1504,7 +1501,7 @@ gs_status gs_render_multi(const gs_flat_scene* scene, const gs_camera* cam, cons
     const auto t1 = std::chrono::steady_clock::now();
     {
         std::lock_guard<std::mutex> lock(m->mu);
-        s = m->render(cam, ss, seed, out, stats);
+        s = m->render(Frame{Session::None, cam, ss, seed, m->th}, out, stats);
     }
     gs_multi_destroy(m);
     if (s == GS_OK && stats) {

@@ -93,6 +93,19 @@ def _outputs(W, H, rgb, rgb8, ppm):
     return out, res, ppm_buf
 
 
+def _result(res, st, ppm_buf=None, views=None):
+    """The tail of a call's result dict: the PPM text when there is one, the frames as [V,H,W,3] for
+    views = (V, H, W), the call's "counters" and its "stats"."""
+    if ppm_buf is not None:
+        res["ppm"] = ppm_buf[0].raw[:ppm_buf[1].value]
+    for k in ("rgb", "rgb8"):
+        if views is not None and k in res:
+            res[k] = res[k].reshape(*views, 3)
+    res["counters"] = st.counters.as_dict()
+    res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+    return res
+
+
 def render_multi(scene, num_gpus=0, seed=1, tile=64, plan=True, rgb=True, rgb8=False, ppm=False, devices=None,
                  bvh="host"):
     """camera.rs:105-114 (and with ppm=True the whole of :100-121) on `num_gpus` GPUs of
@@ -110,11 +123,7 @@ def render_multi(scene, num_gpus=0, seed=1, tile=64, plan=True, rgb=True, rgb8=F
         st = N.gs_stats()
         N.check(N.lib.gs_render_multi(host.flat_ptr, C.byref(cam), C.byref(scene.settings), seed, C.byref(launch),
                                       C.byref(out), C.byref(st)))
-        if ppm:
-            res["ppm"] = ppm_buf[0].raw[:ppm_buf[1].value]
-        res["counters"] = st.counters.as_dict()
-        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
-        return res
+        return _result(res, st, ppm_buf)
     finally:
         host.close()
 
@@ -154,11 +163,7 @@ class MultiRenderer:
         st = N.gs_stats()
         N.check(N.lib.gs_multi_render(self.handle, C.byref(self.cam), C.byref(self.settings), seed,
                                       C.byref(out) if out is not None else None, C.byref(st)))
-        if ppm:
-            res["ppm"] = ppm_buf[0].raw[:ppm_buf[1].value]
-        res["counters"] = st.counters.as_dict()
-        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
-        return res
+        return _result(res, st, ppm_buf)
 
     def render_stats(self, seed, st):
         """One frame, the frame left on the first device, its gs_stats written into `st` (a
@@ -201,12 +206,7 @@ class MultiRenderer:
         st = N.gs_stats()
         N.check(N.lib.gs_multi_render_views(self.handle, views, V, samples, chunk,
                                             C.byref(out) if out is not None else None, C.byref(st)))
-        for k in ("rgb", "rgb8"):
-            if k in res:
-                res[k] = res[k].reshape(V, H, W, 3)
-        res["counters"] = st.counters.as_dict()
-        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
-        return res
+        return _result(res, st, views=(V, H, W))
 
     def render_views_adaptive(self, cameras, seeds=None, settings=None, rgb=True, rgb8=False):
         """V cameras of the context's world under one set of adaptive SampleSettings (default: the
@@ -235,11 +235,8 @@ class MultiRenderer:
             N.check(N.lib.gs_multi_views_adapt_info(self.handle, C.byref(i), None))
         finally:
             N.lib.gs_multi_views_adapt_end(self.handle)
-        for k in ("rgb", "rgb8"):
-            if k in res:
-                res[k] = res[k].reshape(V, H, W, 3)
+        res = _result(res, st, views=(V, H, W))
         res["counters"] = i.counters.as_dict()
-        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
         return res
 
     def scene_info(self, rank=0):
@@ -301,7 +298,42 @@ def render_views(scene, cameras, samples, seeds=None, num_gpus=1, tile=64, devic
         r.close()
 
 
-class ProgressiveRenderer:
+class _Session:
+    """What the four session renderers share: a frame context of their own (self._mr), on which
+    their session is open (self._open) until close(), which ends it with the library's `_end`."""
+
+    _end = None  # the name of the session's gs_multi_*_end
+
+    @property
+    def devices(self):
+        return self._mr.devices
+
+    def scene_info(self, rank=0):
+        return self._mr.scene_info(rank)
+
+    def close(self):
+        mr = getattr(self, "_mr", None)
+        if mr is not None:
+            if self._open and mr.handle:
+                getattr(N.lib, self._end)(mr.handle)
+            self._open = False
+            mr.close()
+            self._mr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
+            pass
+
+
+class ProgressiveRenderer(_Session):
     """A fixed-spp frame rendered in passes (gs_multi_accum_*): every pass adds `samples` more
     samples per pixel to f64 sums resident on the devices and returns the frame resolved so far.
 
@@ -311,6 +343,8 @@ class ProgressiveRenderer:
     resume().  The scene's own SampleSettings are not used: a pass is a sample count (adaptive
     settings have their own pass form, AdaptiveRenderer).  chunk: the coarse sample chunk c (0 = 16); every pass is 1 to
     64 whole chunks."""
+
+    _end = "gs_multi_accum_end"
 
     def __init__(self, scene, num_gpus=1, seed=1, chunk=0, tile=64, plan=True, devices=None, bvh="host",
                  _resume=None):
@@ -344,10 +378,6 @@ class ProgressiveRenderer:
     def height(self):
         return self._mr.height
 
-    @property
-    def devices(self):
-        return self._mr.devices
-
     def _info(self):
         i = N.gs_accum_info()
         N.check(N.lib.gs_multi_accum_info(self._mr.handle, C.byref(i)))
@@ -377,10 +407,7 @@ class ProgressiveRenderer:
         st = N.gs_stats()
         N.check(N.lib.gs_multi_accum_pass(self._mr.handle, int(samples), C.byref(out) if out is not None else None,
                                           C.byref(st)))
-        if ppm:
-            res["ppm"] = ppm_buf[0].raw[:ppm_buf[1].value]
-        res["counters"] = st.counters.as_dict()
-        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+        res = _result(res, st, ppm_buf)
         res["info"] = self.info()
         return res
 
@@ -428,9 +455,6 @@ class ProgressiveRenderer:
         """(device pointer of the last resolved W*H*3 f32 frame or None, its device id)."""
         return self._mr.frame_ptr()
 
-    def scene_info(self, rank=0):
-        return self._mr.scene_info(rank)
-
     def save(self, path):
         """Write a checkpoint (grayshift_amd.checkpoint): the sums, samples, seed, chunk, frame size,
         the gs_camera bytes and the cumulative counters."""
@@ -453,29 +477,8 @@ class ProgressiveRenderer:
         checkpoint.check_compatible(meta, cam.image_width, cam.image_height, chunk, seed, bytes(cam))
         return cls(scene, seed=seed, chunk=chunk, _resume=(sums, meta), **kw)
 
-    def close(self):
-        mr = getattr(self, "_mr", None)
-        if mr is not None:
-            if self._open and mr.handle:
-                N.lib.gs_multi_accum_end(mr.handle)
-            self._open = False
-            mr.close()
-            self._mr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
-            pass
-
-
-class AdaptiveRenderer:
+class AdaptiveRenderer(_Session):
     """The scene's own adaptive SampleSettings rendered in passes of batch rounds
     (gs_multi_adapt_*): round r renders batch r of every pixel still active, and every pass
     returns the frame resolved so far -- a stopped pixel's final colour, an active pixel's mean
@@ -485,6 +488,8 @@ class AdaptiveRenderer:
     resume() in between, the finished frame, its rgb8 bytes and the cumulative counters are those
     of render() / render_multi() with the same settings and seed, bit for bit; after k rounds
     the frame is the one-shot frame with max_samples = k * batch_size - 1."""
+
+    _end = "gs_multi_adapt_end"
 
     def __init__(self, scene, num_gpus=1, seed=1, tile=64, plan=True, devices=None, bvh="host", _resume=None):
         self.scene = scene
@@ -515,10 +520,6 @@ class AdaptiveRenderer:
         return self._mr.height
 
     @property
-    def devices(self):
-        return self._mr.devices
-
-    @property
     def info(self):
         """gs_adapt_info: width, height, batch, rounds, max_rounds, finished, seed, active_pixels,
         samples_total, samples_max and the cumulative counters (attributes; .as_dict())."""
@@ -539,10 +540,7 @@ class AdaptiveRenderer:
         st = N.gs_stats()
         N.check(N.lib.gs_multi_adapt_pass(self._mr.handle, int(n), C.byref(out) if out is not None else None,
                                           C.byref(st)))
-        if ppm:
-            res["ppm"] = ppm_buf[0].raw[:ppm_buf[1].value]
-        res["counters"] = st.counters.as_dict()
-        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+        res = _result(res, st, ppm_buf)
         res["info"] = self.info.as_dict()
         return res
 
@@ -624,29 +622,8 @@ class AdaptiveRenderer:
         checkpoint.check_adaptive_compatible(meta, cam.image_width, cam.image_height, scene.settings, seed, bytes(cam))
         return cls(scene, seed=seed, _resume=(sums, state, meta), **kw)
 
-    def close(self):
-        mr = getattr(self, "_mr", None)
-        if mr is not None:
-            if self._open and mr.handle:
-                N.lib.gs_multi_adapt_end(mr.handle)
-            self._open = False
-            mr.close()
-            self._mr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
-            pass
-
-
-class ViewsProgressiveRenderer:
+class ViewsProgressiveRenderer(_Session):
     """A batch of cameras of one world refined in passes, view by view (gs_multi_views_accum_*):
     every pass adds `samples` more samples per pixel to the f64 sums of a subset of the views and
     returns all V frames resolved so far.
@@ -661,6 +638,8 @@ class ViewsProgressiveRenderer:
     cameras: gs_camera_specs of one width and height; seeds: one per camera (default 1 each);
     chunk: the coarse sample chunk c (0 = 16), every pass is 1 to 64 whole chunks.  The scene's own
     camera and SampleSettings are not used."""
+
+    _end = "gs_multi_views_accum_end"
 
     def __init__(self, scene, cameras, seeds=None, num_gpus=1, chunk=0, tile=64, devices=None, bvh="host",
                  _resume=None):
@@ -695,10 +674,6 @@ class ViewsProgressiveRenderer:
         except Exception:
             self.close()
             raise
-
-    @property
-    def devices(self):
-        return self._mr.devices
 
     def _info(self):
         i = N.gs_views_accum_info()
@@ -838,9 +813,6 @@ class ViewsProgressiveRenderer:
         """(device pointer of the last resolved [V,H,W,3] f32 frames or None, its device id)."""
         return self._mr.frame_ptr()
 
-    def scene_info(self, rank=0):
-        return self._mr.scene_info(rank)
-
     def save(self, path):
         """Write a checkpoint (grayshift_amd.checkpoint, format 3): the sums, the per-view samples,
         seeds and gs_camera bytes, chunk, view size and the cumulative counters."""
@@ -868,29 +840,8 @@ class ViewsProgressiveRenderer:
         r._fresh = np.ones(len(cams), dtype=bool)
         return r
 
-    def close(self):
-        mr = getattr(self, "_mr", None)
-        if mr is not None:
-            if self._open and mr.handle:
-                N.lib.gs_multi_views_accum_end(mr.handle)
-            self._open = False
-            mr.close()
-            self._mr = None
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
-            pass
-
-
-class ViewsAdaptiveRenderer:
+class ViewsAdaptiveRenderer(_Session):
     """A batch of cameras of one world under ONE set of adaptive SampleSettings, in passes of batch
     rounds on the tall frame (gs_multi_views_adapt_*): round r renders batch r of every pixel of
     every view that is still active, so a late round's few surviving pixels of all views share one
@@ -905,6 +856,8 @@ class ViewsAdaptiveRenderer:
 
     cameras: gs_camera_specs of one width and height; seeds: one per camera (default 1 each);
     settings: a gs_sample_settings (default: the scene's own).  The scene's own camera is not used."""
+
+    _end = "gs_multi_views_adapt_end"
 
     def __init__(self, scene, cameras, seeds=None, settings=None, num_gpus=1, tile=64, devices=None, bvh="host",
                  _resume=None):
@@ -937,10 +890,6 @@ class ViewsAdaptiveRenderer:
             self.close()
             raise
 
-    @property
-    def devices(self):
-        return self._mr.devices
-
     def _info(self, active=None):
         i = N.gs_views_adapt_info()
         N.check(N.lib.gs_multi_views_adapt_info(self._mr.handle, C.byref(i),
@@ -971,11 +920,7 @@ class ViewsAdaptiveRenderer:
         st = N.gs_stats()
         N.check(N.lib.gs_multi_views_adapt_pass(self._mr.handle, int(n), C.byref(out) if out is not None else None,
                                                 C.byref(st)))
-        for k in ("rgb", "rgb8"):
-            if k in res:
-                res[k] = res[k].reshape(V, H, W, 3)
-        res["counters"] = st.counters.as_dict()
-        res["stats"] = {k: v for k, v in st.as_dict().items() if k != "counters"}
+        res = _result(res, st, views=(V, H, W))
         res["info"] = self._info().as_dict()
         return res
 
@@ -1031,9 +976,6 @@ class ViewsAdaptiveRenderer:
         """(device pointer of the last resolved [V,H,W,3] f32 frames or None, its device id)."""
         return self._mr.frame_ptr()
 
-    def scene_info(self, rank=0):
-        return self._mr.scene_info(rank)
-
     def save(self, path):
         """Write a checkpoint (grayshift_amd.checkpoint, format 4): the sums and state words, the
         rounds run, the settings, the views' seeds and gs_camera bytes, the view size and the
@@ -1061,27 +1003,6 @@ class ViewsAdaptiveRenderer:
         W, H = (cams[0].image_width, cams[0].image_height) if cams else (0, 0)
         checkpoint.check_views_adaptive_compatible(meta, W, H, settings, seeds, [bytes(c) for c in cams])
         return cls(scene, cameras, seeds=seeds, settings=settings, _resume=(sums, state, meta), **kw)
-
-    def close(self):
-        mr = getattr(self, "_mr", None)
-        if mr is not None:
-            if self._open and mr.handle:
-                N.lib.gs_multi_views_adapt_end(mr.handle)
-            self._open = False
-            mr.close()
-            self._mr = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001  (interpreter shutdown: the binding may be gone)
-            pass
 
 
 def render_views_adaptive(scene, cameras, seeds=None, settings=None, num_gpus=1, tile=64, devices=None, rgb=True,

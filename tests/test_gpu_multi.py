@@ -322,3 +322,69 @@ def test_async_launch_returns_while_the_kernel_runs():
     assert min(waits) > 0.05, waits  # the frames did run long (>= ~100 ms of kernel)
     # (relative, not an absolute bound: a loaded host may take a few ms for the call itself)
     assert max(launches) < 0.1 * min(waits), (launches, waits)
+
+
+def test_sessions_leave_the_context_as_they_found_it():
+    """One context (3 ranks on one device, cost plan on, tile 16, a 40 x 24 frame) through all four
+    session kinds, by the raw C calls: after every session's _end the one-shot frame, its rgb8 bytes
+    and its counters are the ones from before any session -- a views session's own tile height
+    (gs_views_tile_h(24, 16) = 12, not the context's 16) and its round-robin cut leave nothing
+    behind in the context or its cached partition -- and while a session is open a one-shot render
+    and a begin of another kind are refused with that session's message."""
+    import ctypes as C
+    from tests import test_gpu_views_adaptive as VA
+    sc = VA._scene("spheres")  # (40 x 24, batch 4, max_samples 16)
+    cams = VA._family("spheres")[1]
+    L = N.lib
+    N.check(L.gs_debug_set_multi_same_device(1))
+    try:
+        mr = g.MultiRenderer(sc, devices=[0, 0, 0], tile=16, plan=True)
+    finally:
+        N.check(L.gs_debug_set_multi_same_device(0))
+    try:
+        assert (mr.width, mr.height) == (40, 24) and (mr.settings.batch_size, mr.settings.max_samples) == (4, 16)
+        assert L.gs_views_tile_h(24, 16) == 12
+        h, cam, ss = mr.handle, C.byref(mr.cam), C.byref(mr.settings)
+        views = (N.gs_view * 2)()
+        for v in range(2):
+            views[v].cam, views[v].seed = g.camera(cams[v]), 3 + v
+        f0 = mr.render(seed=5, rgb=True, rgb8=True)
+        assert f0["counters"]["pixels"] == 40 * 24 and f0["stats"]["num_gpus"] == 3
+
+        def tile_h(info_type, info_call, *more):
+            i = info_type()
+            N.check(info_call(h, C.byref(i), *more))
+            return i.tile_h
+
+        sessions = (
+            (lambda: L.gs_multi_accum_begin(h, cam, 5, 4), lambda: L.gs_multi_accum_pass(h, 4, None, None),
+             L.gs_multi_accum_end, lambda: L.gs_multi_views_accum_begin(h, views, 2, 4), None,
+             b"an accumulation is open: gs_multi_accum_end first"),
+            (lambda: L.gs_multi_views_accum_begin(h, views, 2, 4),
+             lambda: L.gs_multi_views_accum_pass(h, 4, None, None, None), L.gs_multi_views_accum_end,
+             lambda: L.gs_multi_adapt_begin(h, cam, ss, 5),
+             lambda: tile_h(N.gs_views_accum_info, L.gs_multi_views_accum_info, None, None),
+             b"a views accumulation is open: gs_multi_views_accum_end first"),
+            (lambda: L.gs_multi_adapt_begin(h, cam, ss, 5), lambda: L.gs_multi_adapt_pass(h, 1, None, None),
+             L.gs_multi_adapt_end, lambda: L.gs_multi_accum_begin(h, cam, 5, 4), None,
+             b"an adaptation is open: gs_multi_adapt_end first"),
+            (lambda: L.gs_multi_views_adapt_begin(h, views, 2, ss),
+             lambda: L.gs_multi_views_adapt_pass(h, 1, None, None), L.gs_multi_views_adapt_end,
+             lambda: L.gs_multi_views_accum_begin(h, views, 2, 4),
+             lambda: tile_h(N.gs_views_adapt_info, L.gs_multi_views_adapt_info, None),
+             b"a views adaptation is open: gs_multi_views_adapt_end first"),
+        )
+        for begin, one_pass, end, foreign_begin, session_tile_h, message in sessions:
+            N.check(begin())
+            N.check(one_pass())
+            assert L.gs_multi_render(h, cam, ss, 5, None, None) == N.GS_ERR_ARG and L.gs_last_error() == message
+            assert foreign_begin() == N.GS_ERR_ARG and L.gs_last_error() == message
+            if session_tile_h is not None:
+                assert session_tile_h() == 12
+            N.check(end(h))
+            again = mr.render(seed=5, rgb=True, rgb8=True)
+            assert again["rgb"].tobytes() == f0["rgb"].tobytes(), message
+            assert again["rgb8"].tobytes() == f0["rgb8"].tobytes(), message
+            assert again["counters"] == f0["counters"], message
+    finally:
+        mr.close()

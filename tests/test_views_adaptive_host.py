@@ -155,19 +155,59 @@ def test_context_calls_reject_a_null_context(cam):
 
 
 def test_open_states_are_excluded_in_both_directions_in_the_source():
-    """Without a device no context can be opened; what can be read here: every one of the four
-    begin paths of multi_gpu.cpp refuses while a views adaptation is open, and the views
-    adaptation's begin goes through the adaptation's, which refuses for the three others."""
+    """Without a device no context can be opened; what can be read here: one function of
+    multi_gpu.cpp, gs_multi::admit, holds the refusal for each of the four sessions and refuses
+    whenever one is open, whichever it is; every one of the four begin paths (the adaptation's
+    begin serves the views adaptation too) asks it before anything else, and so does a frame,
+    whose checks come before its first stage; every session call of the header goes through it,
+    and nothing but a begin opens a session.  (Read by shape, not by exact text: the first call a
+    function makes, what follows it, which functions hold what.)"""
     src = open(os.path.join(ROOT, "grayshift_amd", "csrc", "host", "multi_gpu.cpp")).read()
-    refusal = 'if (vd_open) return fail(GS_ERR_ARG, "a views adaptation is open: gs_multi_views_adapt_end first");'
-    for fn in ("gs_multi::accum_begin(", "gs_multi::views_accum_begin(", "gs_multi::adapt_open("):
-        body = src[src.index("gs_status " + fn):]
-        body = body[:body.index("\n}\n")]
-        assert refusal in body, fn
-    body = src[src.index("gs_status gs_multi::adapt_open("):]
-    body = body[:body.index("\n}\n")]
-    for other in ("if (ad_open)", "if (acc_open)", "if (va_open)"):
-        assert other in body, other
+
+    def body_of(name):  # of the function defined as `gs_status <name>(...) [const] {` at the left margin
+        m = re.search(r"^gs_status %s\([^{;]*\{\n" % re.escape(name), src, re.M)
+        assert m, name
+        return src[m.end():src.index("\n}\n", m.end())]
+
+    def first_call(body):
+        return re.search(r"\b(\w+)\s*\(", body).group(1)
+
+    admit = body_of("gs_multi::admit")
+    for message in ("an accumulation is open: gs_multi_accum_end first",
+                    "a views accumulation is open: gs_multi_views_accum_end first",
+                    "an adaptation is open: gs_multi_adapt_end first",
+                    "a views adaptation is open: gs_multi_views_adapt_end first"):
+        assert admit.count(message) == 1, message
+        assert src.count(message) == 1, message  # (nowhere else: no second copy of the rule)
+    # a begin (and a one-shot frame) passes only with no session open; the refusal is the open one's
+    assert re.search(r"if \(open == Session::None\) return GS_OK;", admit)
+    assert re.search(r"refusal\[\(int\)open\]", admit) and re.search(r"return fail\(GS_ERR_ARG, msg\);\s*$", admit)
+    begins = ("gs_multi::accum_begin", "gs_multi::views_accum_begin", "gs_multi::adapt_begin")
+    for fn in begins:
+        body = body_of(fn)
+        assert first_call(body) == "admit", fn
+        assert re.search(r"\bs = admit\(Call::Begin, [\w:]+\);\s*if \(s != GS_OK\) return s;", body), fn
+    render = body_of("gs_multi::render")
+    assert first_call(render) == "check_frame"
+    assert re.search(r"\bs = check_frame\(f, out\);\s*if \(s != GS_OK\) return s;", render)
+    check = body_of("gs_multi::check_frame")
+    assert re.search(r"return admit\(Call::Frame, f\.session\);\s*$", check) and "hip" not in check
+    # every pass, info, maps, download and end of the header is a session's own call: through in_session,
+    # which asks admit under the context's lock before the call's body runs
+    header = open(os.path.join(ROOT, "include", "grayshift_gpu.h")).read()
+    own = set(re.findall(r"\b(gs_multi_(?:views_)?(?:accum|adapt)_(?:pass|info|maps|download|end))\s*\(", header))
+    assert len(own) == 18, sorted(own)
+    for fn in sorted(own):
+        assert re.match(r"\s*(?:if \([^\n]*\) return fail\(GS_ERR_ARG, \"null argument\"\);\s*)?"  # (a null guard at most)
+                        r"return in_session\(m, Session::\w+, Call::(?:Pass|Other),", body_of(fn)), fn
+    gate = src[src.index("gs_status in_session("):]
+    gate = gate[:gate.index("\n}\n")]
+    assert re.search(r"lock_guard.*\n.*m->admit\(call, s\);\s*return st != GS_OK \? st : body\(\);", gate)
+    # only a begin opens a session, and the old parallel flags are gone
+    opened = re.findall(r"\bopen = (?!Session::None;)", src)
+    assert len(opened) == sum(len(re.findall(r"\bopen = (?!Session::None;)", body_of(fn))) for fn in begins) == 3
+    for flag in ("acc_open", "va_open", "ad_open", "vd_open", "th_ctx"):
+        assert flag not in src, flag
 
 
 # ------------------------------------------------------------ records
