@@ -47,6 +47,8 @@ static std::atomic<int32_t> g_round_whole{0};
 #endif
 static const uint64_t kMaxRounds = 1u << 16;  // more batches than this: the per-lane loop
 static std::atomic<int32_t> g_cube_lists{1};  // gs_debug_set_cube_lists
+static std::atomic<int32_t> g_cert_boxes{1};  // gs_debug_set_cert_boxes
+static std::atomic<int64_t> g_mirror_budget{-1};  // gs_debug_set_mirror_budget
 
 Knobs read_knobs() {
     const auto rlx = std::memory_order_relaxed;
@@ -63,6 +65,8 @@ Knobs read_knobs() {
     k.adaptive_rounds = g_adaptive_rounds.load(rlx);
     k.round_whole = g_round_whole.load(rlx);
     k.cube_lists = g_cube_lists.load(rlx);
+    k.cert_boxes = g_cert_boxes.load(rlx);
+    k.mirror_budget = g_mirror_budget.load(rlx);
     return k;
 }
 
@@ -126,6 +130,18 @@ gs_status gs_debug_set_round_items(int32_t mode) {
 gs_status gs_debug_set_cube_lists(int32_t on) {
     if (on != 0 && on != 1) return fail(GS_ERR_ARG, "cube lists are 0 (the list loop) or 1 (cube_test)");
     g_cube_lists = on;
+    return GS_OK;
+}
+
+gs_status gs_debug_set_cert_boxes(int32_t on) {
+    if (on != 0 && on != 1) return fail(GS_ERR_ARG, "cert boxes are 1 (the 1e15 rule decides) or 0 (the f64 box test)");
+    g_cert_boxes = on;
+    return GS_OK;
+}
+
+gs_status gs_debug_set_mirror_budget(int64_t bytes) {
+    if (bytes < -1) return fail(GS_ERR_ARG, "the mirror budget is -1 (the block's own) or a byte count >= 0");
+    g_mirror_budget = bytes;
     return GS_OK;
 }
 

@@ -34,6 +34,8 @@ struct Knobs {
     int32_t adaptive_rounds; // 1 auto (GS_ROUND_MIN_CAP), 2 always rounds, 0 never
     int32_t round_whole;     // work items of a round: 0 split, 1 whole-batch, -1 whole while the lanes fill twice
     int32_t cube_lists;      // gs_debug_set_cube_lists
+    int32_t cert_boxes;      // gs_debug_set_cert_boxes: 1 the 1e15 rule decides, 0 no scene has certified boxes
+    int64_t mirror_budget;   // gs_debug_set_mirror_budget: -1 the block's own budget, >= 0 at most this many bytes
 };
 Knobs read_knobs();
 

@@ -936,7 +936,8 @@ gs_status gs_device_scene_create(const gs_flat_scene* s, gs_device_scene** out) 
 
     std::unique_ptr<gs_device_scene, DestroyScene> ds(new gs_device_scene());
     DeviceArrays a;
-    find_cube_lists(*s, read_knobs().cube_lists != 0, a, ds->single_quads);
+    const Knobs knobs = read_knobs();  // one snapshot of the upload's test hooks
+    find_cube_lists(*s, knobs.cube_lists != 0, a, ds->single_quads);
     ds->n_cubes = (uint32_t)(a.cubes.size() / GS_CUBE_DOUBLES);
     a.insts.assign(s->instances, s->instances + s->n_instances);
     a.media.assign(s->media, s->media + s->n_media);
@@ -951,10 +952,11 @@ gs_status gs_device_scene_create(const gs_flat_scene* s, gs_device_scene** out) 
     score_nested_trees(t, n_top, a.insts, ds->nroot_rec);
 
     ds->mirror_budget = g_lds_mirror < 0 ? lds_mirror_budget() : g_lds_mirror;
+    if (knobs.mirror_budget >= 0) ds->mirror_budget = std::min(knobs.mirror_budget, lds_mirror_budget());  // (test hook)
     Placed pl = place_records(ds.get(), nullptr);
     if (pl.tnodes.size() >= (1u << 26) || pl.tleaves.size() >= (1u << 26))
         return fail(GS_ERR_UNSUPPORTED, "more than 2^26 top-level BVH records");
-    ds->cert_boxes = true;
+    ds->cert_boxes = knobs.cert_boxes != 0;  // (0, a test hook: every node step takes the f64 test)
     for (const TBox& b : pl.tboxes)
         for (double v : {b.mnx, b.mny, b.mnz, b.mxx, b.mxy, b.mxz})
             if (!(std::fabs(v) <= 1e15)) ds->cert_boxes = false;

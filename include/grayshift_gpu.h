@@ -292,6 +292,22 @@ gs_status gs_debug_set_round_items(int32_t mode);
  * compile time (1, default) or with the generic list loop (0).  Both render the same bits. */
 gs_status gs_debug_set_cube_lists(int32_t on);
 
+/* Test hook (additive: the ABI stays 11): scenes uploaded after this call take the certified f32
+ * box test where gs_scene_info.cert_boxes allows it (1, default: every node coordinate
+ * |x| <= 1e15 decides) or never (0: cert_boxes is 0 whatever the coordinates, so every node
+ * step of every launch of the scene takes the reference's f64 box test).  Both render the same
+ * bits and counters.  Other values: GS_ERR_ARG.  Host only; callable without a device. */
+gs_status gs_debug_set_cert_boxes(int32_t on);
+
+/* Test hook (additive: the ABI stays 11): the byte budget of the per-block LDS mirror for scenes
+ * uploaded after this call.  -1 (default): the block's own budget.  bytes >= 0: that many bytes
+ * at most, and never more than the block's own budget; the upload's placement and the pilot's
+ * re-placement fill it, and gs_scene_info reports the prefixes.  A tree the budget cuts loses
+ * feature bit 8 (whole tree in LDS).  Placement never changes a result: every budget renders
+ * the same bits and counters.  Values below -1: GS_ERR_ARG.  Host only; callable without a
+ * device. */
+gs_status gs_debug_set_mirror_budget(int64_t bytes);
+
 /* Test hook: the auto sample-chunk rule's budget for chunk sums (default 4 GiB; 0
  * restores it).  A smaller budget makes renders take the chunk-doubling branch. */
 gs_status gs_debug_set_partial_budget(uint64_t bytes);
