@@ -29,6 +29,15 @@
 #ifndef GS_ROUND_WHOLE_MAX_BATCH
 #define GS_ROUND_WHOLE_MAX_BATCH 256
 #endif
+// A split round's per-sample colours: entry a's sample j at j * n + a (sample-major: the
+// combine's lanes read one contiguous run per sample), or at a * batch + j (pixel-major: a
+// wave's 1-sample items write one contiguous run).  MI355X A2 (round 6): equal render time;
+// fabric writes 20.1 vs 15.0 GB a frame, combine 4.2 vs 5.7 ms a frame (5.7 -> 6.2 ms with the
+// pixels' samples staged through LDS); profiles/r06/ab_A2_round_items.txt.  The one default: the
+// megakernel (render.hip) writes the layout and the pixel stage (pixel.hpp) folds it.
+#ifndef GS_ROUND_PIXEL_MAJOR
+#define GS_ROUND_PIXEL_MAJOR 0
+#endif
 #define GS_NESTED_STACK 32  // max depth of a BVH under a Translate/RotateY chain (a validation bound; the walk is stackless)
 // Kernel feature flags (template argument): scenes without them compile the code out.
 #define GS_FEAT_MEDIA 1   // ConstantMedium leaves (RNG draws inside traversal)
@@ -341,6 +350,11 @@ static_assert(sizeof(gs_view) % 8 == 0 && sizeof(ViewBatch) <= 3072, "gs_views_k
 #define GS_ACCUM_MAX_BLOCKS 2048u
 __host__ __device__ constexpr uint32_t gs_accum_blocks(uint32_t capacity) {
     return capacity == 0u ? 1u : ((capacity - 1u) / 256u + 1u < GS_ACCUM_MAX_BLOCKS ? (capacity - 1u) / 256u + 1u : GS_ACCUM_MAX_BLOCKS);
+}
+// gs_views_order_kernel's grid: one block of 256 per 256 positions up to 1024 blocks (a grid-stride
+// loop past that).
+__host__ __device__ constexpr uint32_t gs_views_order_blocks(uint32_t n_pos) {
+    return (n_pos - 1u) / 256u + 1u < 1024u ? (n_pos - 1u) / 256u + 1u : 1024u;
 }
 
 // Hot kernel arguments: what the traversal loop reads every step.

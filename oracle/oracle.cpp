@@ -872,6 +872,58 @@ struct HDRI { /* camera.rs:251-270 */
 
 static double luminance(const Vec3& v) { return 0.299 * v.x + 0.587 * v.y + 0.144 * v.z; } /* color.rs:31-33 */
 
+/* The batch loop of Camera::sample (camera.rs:135-167) over sample colours that the caller
+ * supplies: next(c) hands out the pixel's next sample colour, or returns false when it has none
+ * left (a tracing caller always has one).  Camera::sample runs it over traced samples and
+ * oracle_sample_fold over given ones, so there is one copy of the additions and the stop test. */
+enum { FOLD_CONVERGED = 1, FOLD_MAX_SAMPLES = 2, FOLD_EXHAUSTED = 3 };
+struct FoldResult {
+    Vec3 color;       /* pixel_color / sample_count (:167) */
+    uint32_t batches; /* whole batches taken */
+    int reason;       /* FOLD_* */
+};
+/* sums (nullable): after batch k < sums_cap, sums[5 k ..] = pixel_color, sum, sq_sum. */
+template <class Next>
+static FoldResult sample_fold(const gs_sample_settings& ss, Next&& next, double* sums = nullptr, uint32_t sums_cap = 0) {
+    Vec3 pixel_color(0, 0, 0);
+    double tolerance_sq = ss.tolerance * ss.tolerance;
+    double confidence_sq = ss.confidence * ss.confidence;
+    double sum = 0.0, sq_sum = 0.0, sample_count = 0.0;
+    FoldResult res;
+    res.batches = 0;
+    for (;;) {
+        sample_count += (double)ss.batch_size;
+        bool dry = false;
+        for (uint32_t b = 0; b < ss.batch_size; b++) {
+            Vec3 sample_color;
+            if (!next(sample_color)) { dry = true; break; }
+            pixel_color += sample_color;
+            double lum = luminance(sample_color);
+            sum += lum;
+            sq_sum += lum * lum;
+        }
+        if (dry) { /* (the stream ended: the caller gave whole batches, so none of this one was added) */
+            sample_count -= (double)ss.batch_size;
+            res.reason = FOLD_EXHAUSTED;
+            break;
+        }
+        if (sums && res.batches < sums_cap) {
+            double* s = sums + 5 * (size_t)res.batches;
+            s[0] = pixel_color.x; s[1] = pixel_color.y; s[2] = pixel_color.z; s[3] = sum; s[4] = sq_sum;
+        }
+        res.batches++;
+        double mean = sum / sample_count;
+        double variance_sq = 1.0 / (sample_count - 1.0) * (sq_sum - sum * sum / sample_count);
+        double convergence_sq = confidence_sq * variance_sq / sample_count;
+        if (convergence_sq < (mean * mean * tolerance_sq)) { res.reason = FOLD_CONVERGED; break; }
+        /* `sample_count as u32` saturates */
+        if ((uint32_t)sat_u64(sample_count, UINT32_MAX) > ss.max_samples) { res.reason = FOLD_MAX_SAMPLES; break; }
+    }
+    pixel_color /= sample_count;
+    res.color = pixel_color;
+    return res;
+}
+
 struct Camera { /* camera.rs:17-98 */
     int32_t image_width, image_height;
     gs_sample_settings ss;
@@ -952,34 +1004,17 @@ struct Camera { /* camera.rs:17-98 */
         return sample_background(ray);
     }
     Vec3 sample(int32_t i, int32_t j, const Hittable& world) const { /* :125-171 */
-        Vec3 pixel_color(0, 0, 0);
-        double tolerance_sq = ss.tolerance * ss.tolerance;
-        double confidence_sq = ss.confidence * ss.confidence;
-        double sum = 0.0, sq_sum = 0.0, sample_count = 0.0;
         uint32_t pixel = (uint32_t)j * (uint32_t)image_width + (uint32_t)i;
         uint32_t sample_index = 0;
-        for (;;) {
-            sample_count += (double)ss.batch_size;
-            for (uint32_t b = 0; b < ss.batch_size; b++) {
-                tl_rng.state = stream_seed(seed, pixel, sample_index++); /* the seeded stream */
-                tl_cnt.paths++;
-                Ray ray = get_ray(i, j);
-                Vec3 sample_color = ray_color(ray, max_depth, world);
-                pixel_color += sample_color;
-                double lum = luminance(sample_color);
-                sum += lum;
-                sq_sum += lum * lum;
-            }
-            double mean = sum / sample_count;
-            double variance_sq = 1.0 / (sample_count - 1.0) * (sq_sum - sum * sum / sample_count);
-            double convergence_sq = confidence_sq * variance_sq / sample_count;
-            if (convergence_sq < (mean * mean * tolerance_sq)) break;
-            /* `sample_count as u32` saturates */
-            if ((uint32_t)sat_u64(sample_count, UINT32_MAX) > ss.max_samples) break;
-        }
-        pixel_color /= sample_count;
+        const FoldResult res = sample_fold(ss, [&](Vec3& sample_color) { /* :139-140 */
+            tl_rng.state = stream_seed(seed, pixel, sample_index++); /* the seeded stream */
+            tl_cnt.paths++;
+            Ray ray = get_ray(i, j);
+            sample_color = ray_color(ray, max_depth, world);
+            return true;
+        });
         tl_cnt.pixels++;
-        return pixel_color;
+        return res.color;
     }
 };
 
@@ -1443,6 +1478,41 @@ int oracle_background(const void* world, int64_t n, const double* dir, double* o
         Vec3 c = bw.cam->sample_background(Ray(Vec3(), Vec3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]), 0.0));
         out[3 * i] = c.x; out[3 * i + 1] = c.y; out[3 * i + 2] = c.z;
         cnt[i] = tl_cnt.hdri_texels;
+    }
+    return 0;
+}
+
+/* Camera::sample's batch loop (sample_fold) over given sample colours, pixel by pixel.  Pixel i
+ * has the settings (confidence[i], tolerance[i], batch_size, max_samples[i]) and the stream
+ * samples[(i * n_samples + s) * 3 ..], s < n_samples, a whole number of batches.  Out:
+ * batches[i] taken; reason[i] (1 converged, 2 past max_samples, 3 the stream ended first);
+ * color[3 i ..] = pixel_color / sample_count; sums[(i * (n_samples / batch_size) + k) * 5 ..] =
+ * pixel_color, sum, sq_sum after batch k (rows of batches not taken are left as they were). */
+int oracle_sample_fold(int64_t n, uint32_t batch_size, int64_t n_samples, const double* confidence,
+                       const double* tolerance, const uint32_t* max_samples, const double* samples,
+                       uint32_t* batches, int32_t* reason, double* color, double* sums) {
+    if (n < 0 || batch_size == 0 || n_samples < 0 || n_samples % batch_size != 0) {
+        tl_err = "sample_fold: the stream must be a whole number of batches";
+        return -1;
+    }
+    const uint32_t cap = (uint32_t)(n_samples / batch_size);
+    for (int64_t i = 0; i < n; i++) {
+        gs_sample_settings ss;
+        ss.confidence = confidence[i];
+        ss.tolerance = tolerance[i];
+        ss.batch_size = batch_size;
+        ss.max_samples = max_samples[i];
+        const double* src = samples + (size_t)i * (size_t)n_samples * 3;
+        int64_t s = 0;
+        const FoldResult r = sample_fold(ss, [&](Vec3& c) {
+            if (s >= n_samples) return false;
+            c = Vec3(src[3 * s], src[3 * s + 1], src[3 * s + 2]);
+            s++;
+            return true;
+        }, sums + (size_t)i * cap * 5, cap);
+        batches[i] = r.batches;
+        reason[i] = r.reason;
+        color[3 * i] = r.color.x; color[3 * i + 1] = r.color.y; color[3 * i + 2] = r.color.z;
     }
     return 0;
 }

@@ -66,6 +66,7 @@ def lib():
         L.oracle_hit.argtypes = [P, C.c_int64, P, P, P, P, P, P, P, P]
         L.oracle_texture_value.argtypes = [P, C.c_int64, P, P, P, P]
         L.oracle_background.argtypes = [P, C.c_int64, P, P, P]
+        L.oracle_sample_fold.argtypes = [C.c_int64, C.c_uint32, C.c_int64, P, P, P, P, P, P, P, P]
         _lib = L
     return _lib
 
@@ -303,6 +304,32 @@ def luminance(c):
 
 def color_byte(c):
     return lib().oracle_color_byte(c)
+
+
+FOLD_CONVERGED, FOLD_MAX_SAMPLES, FOLD_EXHAUSTED = 1, 2, 3
+
+
+def sample_fold(samples, batch_size, confidence, tolerance, max_samples):
+    """Camera::sample's batch loop over given sample colours: samples [n, S, 3] f64, S a whole
+    number of batches; confidence, tolerance, max_samples scalars or [n].  Returns a dict:
+    batches [n] u32 (taken), reason [n] (FOLD_*), color [n,3] f64 (pixel_color / sample_count) and
+    sums [n, S / batch_size, 5] f64 (pixel_color, sum, sq_sum after each batch; NaN rows for
+    batches not taken)."""
+    samples = np.ascontiguousarray(samples, dtype=np.float64)
+    n, S = samples.shape[0], samples.shape[1]
+    assert samples.shape == (n, S, 3) and batch_size >= 1 and S % batch_size == 0
+    conf = np.ascontiguousarray(np.broadcast_to(np.asarray(confidence, dtype=np.float64), (n,)))
+    tol = np.ascontiguousarray(np.broadcast_to(np.asarray(tolerance, dtype=np.float64), (n,)))
+    mx = np.ascontiguousarray(np.broadcast_to(np.asarray(max_samples, dtype=np.uint32), (n,)))
+    batches = np.zeros(n, dtype=np.uint32)
+    reason = np.zeros(n, dtype=np.int32)
+    color = np.zeros((n, 3))
+    sums = np.full((n, S // batch_size, 5), np.nan)
+    if lib().oracle_sample_fold(n, batch_size, S, conf.ctypes.data, tol.ctypes.data, mx.ctypes.data,
+                                samples.ctypes.data, batches.ctypes.data, reason.ctypes.data, color.ctypes.data,
+                                sums.ctypes.data) != 0:
+        raise RuntimeError("oracle: " + lib().oracle_last_error().decode())
+    return {"batches": batches, "reason": reason, "color": color, "sums": sums}
 
 
 def checker_even(scale, p):

@@ -3,12 +3,14 @@
 // tests/test_gpu_device_kat.py can compare them bit-for-bit with the CPU oracle on
 // adversarial inputs (zero / negative-zero direction components, origins on slab
 // planes, tangent rays, closed/open interval ends), the shading stage (shading.hpp) for
-// tests/test_gpu_shading_kat.py and the leaf stage (leaf.hpp) for tests/test_gpu_leaf_kat.py.
+// tests/test_gpu_shading_kat.py, the leaf stage (leaf.hpp) for tests/test_gpu_leaf_kat.py and the
+// pixel stage's kernels (pixel.hpp) for tests/test_gpu_pixel_kat.py.
 // Not part of the product.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 
 #include "../../grayshift_amd/csrc/device/devmath.hpp"
 #include "../../grayshift_amd/csrc/device/geometry.hpp"
@@ -18,6 +20,7 @@ using namespace gsd;
 
 #include "../../grayshift_amd/csrc/device/leaf.hpp"     // (after the using-directive, as render.hip)
 #include "../../grayshift_amd/csrc/device/shading.hpp"  // (after the using-directive: shading.hpp)
+#include "../../grayshift_amd/csrc/device/pixel.hpp"    // (the pixel stage's kernels, launched as they are)
 
 __global__ void k_aabb(int n, const double* box, const double* ray, const double* iv, int* out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -829,6 +832,483 @@ int kat_leaf(int n, int which, const void* scene, const void* tquads, uint32_t n
     back(cnt, dcnt, C_N * N);
     back(nonuni, dnu, 1);
     (void)hipFree(df); (void)hipFree(dr); (void)hipFree(di); (void)hipFree(dg);
+    return rc;
+}
+
+}  // extern "C"
+
+// ---- the pixel stage (pixel.hpp): the product's kernels themselves, launched with 256 threads as
+// the launchers launch them, over a KParams filled from plain host arrays.  Every entry checks its
+// arguments first -- tile orders, active lists, buffer lengths, segment bounds -- and returns -2
+// without a launch when one is off, so a malformed case never reaches the device; -1 after a HIP
+// error; 0 otherwise.  Every buffer a kernel can write is an in/out array: the caller's contents
+// (its poison pattern) go up before the launch and the buffer comes back after it.
+struct KatPixelLayout {
+    int32_t W, H, tile_w, tile_h, world, rank;  // the frame (for views: the tall one), the tiles, the partition
+    uint32_t slots;   // tile slots of this rank: capacity = slots * tile_w * tile_h
+    uint32_t n_pos;   // entries of order (and of vorder)
+    uint32_t direct;  // out / out8 are the W x H frame (n_out = W H), else packed (n_out = capacity)
+    uint32_t bs, chunk, cpp, fine_px, fine_base;
+    uint32_t max_samples;
+    uint32_t cap;     // the capacity the caller sized its per-pixel arrays for (accum, pstate, pbatches, the
+                      // lists, the maps: their lengths below are multiples of it); must be slots * tile_w * tile_h
+    double confidence, tolerance;
+    const int32_t* order;  // n_pos entries (-1 or a tile of the frame), or null
+    float* out;            // n_out * 3, in/out, or null
+    uint8_t* out8;         // n_out * 3, in/out, or null
+    uint64_t n_out;
+};
+
+namespace {
+
+constexpr uint32_t PX_MAX_CAP = 1u << 22;  // packed pixels a case may have
+
+struct PxCtx {
+    KParams kp;
+    uint32_t cap, tile_px, n_tiles;
+    size_t n_out;
+    int32_t* d_order;
+    float* d_out;
+    uint8_t* d_out8;
+    const KatPixelLayout* L;
+};
+
+bool px_order_ok(const int32_t* o, uint32_t n, uint32_t n_tiles) {
+    for (uint32_t k = 0; k < n; k++)
+        if (!(o[k] == -1 || (o[k] >= 0 && (uint32_t)o[k] < n_tiles))) return false;
+    return true;
+}
+
+// packed_pixel on the host, for the checks: is packed slot k a pixel of the frame?
+bool px_real(const KatPixelLayout* L, const int32_t* order, uint32_t k) {
+    const uint32_t tile_px = (uint32_t)(L->tile_w * L->tile_h), tiles_x = ((uint32_t)L->W + L->tile_w - 1u) / L->tile_w;
+    const uint32_t slot = k / tile_px, w = k % tile_px;
+    const uint32_t pos = (uint32_t)L->rank + slot * (uint32_t)L->world;
+    const int64_t tile = order ? order[pos] : (int64_t)pos;
+    if (tile < 0) return false;
+    const uint64_t pi = (uint64_t)(tile % tiles_x) * L->tile_w + w % L->tile_w;
+    const uint64_t pj = (uint64_t)(tile / tiles_x) * L->tile_h + w / L->tile_w;
+    return pi < (uint64_t)L->W && pj < (uint64_t)L->H;
+}
+
+// The layout's checks and the KParams they allow; the order and the outputs go up.
+int px_begin(const KatPixelLayout* L, PxCtx& c) {
+    std::memset(&c, 0, sizeof(c));
+    if (!L) return -2;
+    if (L->W < 1 || L->H < 1 || L->W > 32768 || L->H > 32768 || L->tile_w < 1 || L->tile_h < 1 || L->tile_w > 1024 ||
+        L->tile_h > 1024 || L->world < 1 || L->world > 1024 || L->rank < 0 || L->rank >= L->world || L->slots < 1 ||
+        L->bs < 1 || L->direct > 1u)
+        return -2;
+    const uint64_t tile_px = (uint64_t)L->tile_w * L->tile_h, cap = tile_px * L->slots;
+    if (cap > PX_MAX_CAP || (uint64_t)L->cap != cap) return -2;
+    const uint32_t tiles_x = ((uint32_t)L->W + L->tile_w - 1u) / L->tile_w, tiles_y = ((uint32_t)L->H + L->tile_h - 1u) / L->tile_h;
+    const uint64_t last_pos = (uint64_t)L->rank + (uint64_t)(L->slots - 1u) * L->world;
+    if (last_pos >= (1ull << 31) || (L->order && last_pos >= L->n_pos)) return -2;
+    if (L->order && !px_order_ok(L->order, L->n_pos, tiles_x * tiles_y)) return -2;
+    if (L->n_out != (L->direct ? (uint64_t)L->W * L->H : cap)) return -2;
+    c.L = L;
+    c.cap = (uint32_t)cap;
+    c.tile_px = (uint32_t)tile_px;
+    c.n_tiles = tiles_x * tiles_y;
+    c.n_out = (size_t)L->n_out;
+    KParams& kp = c.kp;
+    kp.cam.image_width = L->W;
+    kp.cam.image_height = L->H;
+    kp.ss.confidence = L->confidence;
+    kp.ss.tolerance = L->tolerance;
+    kp.ss.batch_size = L->bs;
+    kp.ss.max_samples = L->max_samples;
+    kp.rank = L->rank;
+    kp.world_size = L->world;
+    kp.tile_w = L->tile_w;
+    kp.tile_h = L->tile_h;
+    kp.tiles_x = (int32_t)tiles_x;
+    kp.capacity = c.cap;
+    kp.chunk = L->chunk;
+    kp.cpp = L->cpp;
+    kp.fine_px = L->fine_px;
+    kp.fine_base = L->fine_base;
+    kp.u_cpp = udiv_make(L->cpp ? L->cpp : 1u);
+    kp.u_tpx = udiv_make(c.tile_px);
+    kp.u_tw = udiv_make((uint32_t)L->tile_w);
+    kp.u_tx = udiv_make(tiles_x);
+    kp.u_w = udiv_make((uint32_t)L->W);
+    kp.direct = L->direct;
+    if (L->order) kp.order = c.d_order = dcopy(L->order, L->n_pos);
+    if (L->out) kp.out = c.d_out = dcopy(L->out, c.n_out * 3);
+    if (L->out8) kp.out8 = c.d_out8 = dcopy(L->out8, c.n_out * 3);
+    if ((L->order && !c.d_order) || (L->out && !c.d_out) || (L->out8 && !c.d_out8)) {
+        (void)hipFree(c.d_order); (void)hipFree(c.d_out); (void)hipFree(c.d_out8);
+        return -1;
+    }
+    return 0;
+}
+
+// The doubles of `partial` that the chunk sums of a combine over this layout may touch; 0: the
+// chunking itself is off (no chunks per pixel, a fine region without a chunk size).
+uint64_t px_partial_need(const KatPixelLayout* L, uint32_t cap) {
+    if (L->fine_px > cap) return 0;
+    uint64_t need = 3;
+    if (L->fine_px > 0) {
+        if (L->cpp < 1 || L->cpp > 4096) return 0;
+        need = (uint64_t)L->fine_px * L->cpp * 3;
+    }
+    if (L->fine_px < cap) {
+        if (L->chunk < 1 || L->bs > 4096) return 0;
+        const uint64_t f = ((uint64_t)L->fine_base + (uint64_t)L->bs * (cap - L->fine_px)) * 3;
+        need = f > need ? f : need;
+    }
+    return need;
+}
+
+// Syncs, brings the outputs back (or, without `download`, only frees them) and ends the context.
+int px_end(PxCtx& c, bool download = true) {
+    const hipError_t e = hipDeviceSynchronize();
+    const int rc = e == hipSuccess && hipGetLastError() == hipSuccess ? 0 : -1;
+    if (c.d_out) { if (download && rc == 0) (void)hipMemcpy(c.L->out, c.d_out, c.n_out * 3 * sizeof(float), hipMemcpyDeviceToHost); (void)hipFree(c.d_out); }
+    if (c.d_out8) { if (download && rc == 0) (void)hipMemcpy(c.L->out8, c.d_out8, c.n_out * 3, hipMemcpyDeviceToHost); (void)hipFree(c.d_out8); }
+    (void)hipFree(c.d_order);
+    return rc;
+}
+
+// A host array's device copy that comes back when the scope ends well (in/out), or is only freed.
+template <class T>
+struct PxBuf {
+    T* h;
+    T* d;
+    size_t n;
+    bool out;
+    PxBuf(T* host, size_t count, bool is_out) : h(host), d(host ? dcopy(host, count) : nullptr), n(count), out(is_out) {}
+    PxBuf(const PxBuf&) = delete;
+    bool bad() const { return h && !d; }
+    void finish(int rc) {
+        if (d && out && rc == 0) (void)hipMemcpy(h, d, n * sizeof(T), hipMemcpyDeviceToHost);
+        (void)hipFree(d);
+        d = nullptr;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int kat_pixel_layout_bytes(void) { return (int)sizeof(KatPixelLayout); }
+uint32_t kat_pixel_accum_blocks(uint32_t capacity) { return gs_accum_blocks(capacity); }
+uint32_t kat_pixel_stopped_bit(void) { return GS_ADAPT_STOPPED; }
+
+// gs_combine_kernel over grid blocks.  partial: n_partial doubles.
+int kat_pixel_combine(const KatPixelLayout* L, uint32_t grid, const double* partial, uint64_t n_partial) {
+    PxCtx c;
+    if (grid < 1 || grid > 65536u || !partial) return -2;
+    int rc = px_begin(L, c);
+    if (rc) return rc;
+    const uint64_t need = px_partial_need(L, c.cap);
+    if (need == 0 || n_partial < need) { (void)px_end(c, false); return -2; }
+    PxBuf<double> dp(const_cast<double*>(partial), (size_t)n_partial, false);
+    c.kp.partial = dp.d;
+    KParams* dP = dcopy(&c.kp, 1);
+    if (!dp.bad() && dP) hipLaunchKernelGGL(gs_combine_kernel, dim3(grid), dim3(256), 0, 0, dP);
+    rc = px_end(c);
+    if (dp.bad() || !dP) rc = -1;
+    dp.finish(rc);
+    (void)hipFree(dP);
+    return rc;
+}
+
+// gs_accumulate_kernel, n_pass passes chained on the device: pass p has sample_base p * bs and the
+// sums partial[p * n_partial ..]; accum (capacity * 3, in: the sums before pass 0) stays on the
+// device between the passes.  After pass p: accum_out[p], out_all / out8_all[p] (n_out * 3 each;
+// before each pass the outputs are set to the layout's out / out8 again) and delta_out[p]
+// (gs_accum_blocks(capacity) doubles; null: the kernel runs with delta null).
+int kat_pixel_accumulate(const KatPixelLayout* L, uint32_t n_pass, const double* partial, uint64_t n_partial,
+                         const double* accum, double* accum_out, float* out_all, uint8_t* out8_all, double* delta_out) {
+    PxCtx c;
+    if (n_pass < 1 || n_pass > 16 || !partial || !accum || !accum_out) return -2;
+    if (!L || (L->out && !out_all) || (L->out8 && !out8_all) || (uint64_t)L->bs * n_pass > 0xFFFFFFFFull) return -2;
+    int rc = px_begin(L, c);
+    if (rc) return rc;
+    const uint64_t need = px_partial_need(L, c.cap);
+    if (need == 0 || n_partial < need) { (void)px_end(c, false); return -2; }
+    const uint32_t blocks = gs_accum_blocks(c.cap);
+    const size_t n3 = (size_t)c.cap * 3, o3 = c.n_out * 3;
+    PxBuf<double> dp(const_cast<double*>(partial), (size_t)n_partial * n_pass, false);
+    PxBuf<double> da(const_cast<double*>(accum), n3, false);
+    double* dd = delta_out ? dcopy(delta_out, blocks) : nullptr;
+    KParams* dP = dcopy(&c.kp, 1);
+    bool ok = !dp.bad() && !da.bad() && dP && (!delta_out || dd);
+    for (uint32_t p = 0; ok && p < n_pass; p++) {
+        c.kp.partial = dp.d + (size_t)p * n_partial;
+        c.kp.accum = da.d;
+        c.kp.delta = dd;
+        c.kp.sample_base = p * L->bs;
+        ok = hipMemcpy(dP, &c.kp, sizeof(KParams), hipMemcpyHostToDevice) == hipSuccess;
+        if (ok && dd) ok = hipMemcpy(dd, delta_out + (size_t)p * blocks, blocks * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+        if (ok && c.d_out) ok = hipMemcpy(c.d_out, L->out, o3 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+        if (ok && c.d_out8) ok = hipMemcpy(c.d_out8, L->out8, o3, hipMemcpyHostToDevice) == hipSuccess;
+        if (!ok) break;
+        hipLaunchKernelGGL(gs_accumulate_kernel, dim3(blocks), dim3(256), 0, 0, dP);
+        ok = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
+        if (!ok) break;  // (after a HIP error nothing more is launched)
+        (void)hipMemcpy(accum_out + (size_t)p * n3, da.d, n3 * sizeof(double), hipMemcpyDeviceToHost);
+        if (dd) (void)hipMemcpy(delta_out + (size_t)p * blocks, dd, blocks * sizeof(double), hipMemcpyDeviceToHost);
+        if (c.d_out) (void)hipMemcpy(out_all + (size_t)p * o3, c.d_out, o3 * sizeof(float), hipMemcpyDeviceToHost);
+        if (c.d_out8) (void)hipMemcpy(out8_all + (size_t)p * o3, c.d_out8, o3, hipMemcpyDeviceToHost);
+    }
+    rc = px_end(c, false);
+    if (!ok) rc = -1;
+    dp.finish(rc);
+    da.finish(rc);
+    (void)hipFree(dd);
+    (void)hipFree(dP);
+    return rc;
+}
+
+// The views of a pass: V views of W x view_h stacked (L->H = V * view_h, tile_h | view_h), vstate
+// {before, selected} per view, vorder n_pos entries or null.
+static int px_views_ok(const KatPixelLayout* L, const PxCtx& c, const int32_t* vorder, const uint32_t* vstate, uint32_t V,
+                       uint32_t view_h) {
+    if (!vstate || V < 1 || V > 4096 || view_h < 1 || (uint64_t)V * view_h != (uint64_t)L->H) return -2;
+    if (view_h % (uint32_t)L->tile_h != 0) return -2;  // tiles do not straddle views
+    for (uint32_t v = 0; v < V; v++)
+        if (vstate[2 * v + 1] > 1u || (uint64_t)vstate[2 * v] + L->bs > 0xFFFFFFFFull) return -2;
+    if (vorder && !px_order_ok(vorder, L->n_pos, c.n_tiles)) return -2;
+    return 0;
+}
+
+// gs_views_order_kernel: dst (n_pos entries, in/out) over gs_views_order_blocks(n_pos) blocks, as
+// launch_views_order_kernel.
+int kat_pixel_views_order(const KatPixelLayout* L, const int32_t* vorder, const uint32_t* vstate, uint32_t V,
+                          uint32_t view_h, int32_t* dst) {
+    PxCtx c;
+    if (!dst || !L || L->n_pos < 1 || L->n_pos > PX_MAX_CAP) return -2;
+    int rc = px_begin(L, c);
+    if (rc) return rc;
+    if (px_views_ok(L, c, vorder, vstate, V, view_h) != 0) { (void)px_end(c, false); return -2; }
+    PxBuf<int32_t> dvo(const_cast<int32_t*>(vorder), L->n_pos, false);
+    PxBuf<uint32_t> dvs(const_cast<uint32_t*>(vstate), 2 * (size_t)V, false);
+    PxBuf<int32_t> dd(dst, L->n_pos, true);
+    c.kp.vorder = dvo.d;
+    c.kp.vstate = reinterpret_cast<const GsViewState*>(dvs.d);
+    KParams* dP = dcopy(&c.kp, 1);
+    const bool ok = !dvo.bad() && !dvs.bad() && !dd.bad() && dP;
+    if (ok) hipLaunchKernelGGL(gs_views_order_kernel, dim3(gs_views_order_blocks(L->n_pos)), dim3(256), 0, 0, dP, dd.d, L->n_pos, view_h);
+    rc = px_end(c, false);
+    if (!ok) rc = -1;
+    dvo.finish(rc); dvs.finish(rc); dd.finish(rc);
+    (void)hipFree(dP);
+    return rc;
+}
+
+// gs_views_accumulate_kernel, one block per slot.  accum (capacity * 3) and vdelta (slots; null:
+// the kernel runs with vdelta null) are in/out.
+int kat_pixel_views_accumulate(const KatPixelLayout* L, const int32_t* vorder, const uint32_t* vstate, uint32_t V,
+                               uint32_t view_h, const double* partial, uint64_t n_partial, double* accum,
+                               double* vdelta) {
+    PxCtx c;
+    if (!partial || !accum || !L) return -2;
+    if (vorder && ((uint64_t)L->rank + (uint64_t)(L->slots - 1u) * L->world >= L->n_pos)) return -2;
+    int rc = px_begin(L, c);
+    if (rc) return rc;
+    const uint64_t need = px_partial_need(L, c.cap);
+    if (px_views_ok(L, c, vorder, vstate, V, view_h) != 0 || need == 0 || n_partial < need) { (void)px_end(c, false); return -2; }
+    PxBuf<int32_t> dvo(const_cast<int32_t*>(vorder), L->n_pos, false);
+    PxBuf<uint32_t> dvs(const_cast<uint32_t*>(vstate), 2 * (size_t)V, false);
+    PxBuf<double> dp(const_cast<double*>(partial), (size_t)n_partial, false);
+    PxBuf<double> da(accum, (size_t)c.cap * 3, true);
+    PxBuf<double> dv(vdelta, L->slots, true);
+    c.kp.vorder = dvo.d;
+    c.kp.vstate = reinterpret_cast<const GsViewState*>(dvs.d);
+    c.kp.u_vpx = udiv_make((uint32_t)L->W * view_h);
+    c.kp.partial = dp.d;
+    c.kp.accum = da.d;
+    c.kp.vdelta = dv.d;
+    KParams* dP = dcopy(&c.kp, 1);
+    const bool ok = !dvo.bad() && !dvs.bad() && !dp.bad() && !da.bad() && !dv.bad() && dP;
+    if (ok) hipLaunchKernelGGL(gs_views_accumulate_kernel, dim3(L->slots), dim3(256), 0, 0, dP);
+    rc = px_end(c);
+    if (!ok) rc = -1;
+    dvo.finish(rc); dvs.finish(rc); dp.finish(rc); da.finish(rc); dv.finish(rc);
+    (void)hipFree(dP);
+    return rc;
+}
+
+// gs_round_init_kernel over grid blocks: active (capacity entries, in/out) and count (1 word,
+// in/out: round_counts[0], 0 before the kernel as the launches leave it).
+int kat_pixel_round_init(const KatPixelLayout* L, uint32_t grid, uint32_t* active, uint32_t* count) {
+    PxCtx c;
+    if (grid < 1 || grid > 65536u || !active || !count || *count != 0u) return -2;
+    int rc = px_begin(L, c);
+    if (rc) return rc;
+    PxBuf<uint32_t> dl(active, c.cap, true);
+    PxBuf<uint32_t> dc(count, 1, true);
+    c.kp.active_buf[0] = dl.d;
+    c.kp.round_counts = dc.d;
+    KParams* dP = dcopy(&c.kp, 1);
+    const bool ok = !dl.bad() && !dc.bad() && dP;
+    if (ok) hipLaunchKernelGGL(gs_round_init_kernel, dim3(grid), dim3(256), 0, 0, dP);
+    rc = px_end(c);
+    if (!ok) rc = -1;
+    dl.finish(rc); dc.finish(rc);
+    (void)hipFree(dP);
+    return rc;
+}
+
+// gs_round_params_kernel (one block of 64, as launch_round_params_kernel).  in: round, seg, seg_px,
+// chunk_req, whole_mode, bs, lanes, waves, capacity, n_act (round_counts[round]), has_counters,
+// poison (the word every field the kernel writes holds before it).  counters: rays, paths (read
+// with has_counters).  hint: rpp_hint[2], in/out.  out (24 words): per_sample, chunk, round, cpp,
+// u_cpp {d, m, s1, s2}, n_items, fine_base, fine_px, claim, claim_fine, round_base, seg_base, seg_n,
+// the list `active` names (0 / 1; 2: neither), the list `next_active` names, the queue word.
+#define KAT_PARAMS_IN 12
+#define KAT_PARAMS_OUT 24
+int kat_pixel_round_params(const uint32_t* in, const unsigned long long* counters, unsigned long long* hint,
+                           uint32_t* out) {
+    if (!in || !counters || !hint || !out) return -2;
+    const uint32_t round = in[0], seg = in[1], seg_px = in[2], bs = in[5], lanes = in[6], waves = in[7], cap = in[8],
+                   n_act = in[9], has_counters = in[10], poison = in[11];
+    if (round > 4096u || bs < 1 || (uint64_t)seg * seg_px > 0xFFFFFFFFull || (uint64_t)round * bs > 0xFFFFFFFFull ||
+        has_counters > 1u)
+        return -2;
+    KParams kp;
+    std::memset(&kp, 0, sizeof(kp));
+    kp.ss.batch_size = bs;
+    kp.lanes = lanes;
+    kp.waves = waves;
+    kp.capacity = cap;
+    kp.per_sample = kp.chunk = kp.round = kp.cpp = kp.n_items = kp.fine_base = kp.fine_px = kp.claim = kp.claim_fine =
+        kp.round_base = kp.seg_base = kp.seg_n = poison;
+    kp.u_cpp = UDiv{poison, poison, poison, poison};
+    unsigned long long cnt[C_N] = {};
+    cnt[C_RAYS] = counters[0];
+    cnt[C_PATHS] = counters[1];
+    uint32_t* counts = new uint32_t[(size_t)round + 1]();
+    counts[round] = n_act;
+    PxBuf<uint32_t> dcounts(counts, (size_t)round + 1, false);
+    PxBuf<unsigned long long> dcnt(cnt, C_N, false);
+    PxBuf<unsigned long long> dh(hint, 2, true);
+    uint32_t lists[2] = {0u, 0u}, q = poison;
+    PxBuf<uint32_t> dl0(&lists[0], 1, false), dl1(&lists[1], 1, false), dq(&q, 1, true);
+    kp.round_counts = dcounts.d;
+    kp.counters = has_counters ? dcnt.d : nullptr;
+    kp.rpp_hint = dh.d;
+    kp.active_buf[0] = dl0.d;
+    kp.active_buf[1] = dl1.d;
+    kp.queue = dq.d;
+    KParams* dP = dcopy(&kp, 1);
+    const bool ok = !dcounts.bad() && !dcnt.bad() && !dh.bad() && !dl0.bad() && !dl1.bad() && !dq.bad() && dP;
+    if (ok)
+        hipLaunchKernelGGL(gs_round_params_kernel, dim3(1), dim3(64), 0, 0, dP, round, seg, seg_px, (int32_t)in[3],
+                           (int32_t)in[4]);
+    int rc = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess && ok ? 0 : -1;
+    KParams r;
+    if (rc == 0 && hipMemcpy(&r, dP, sizeof(KParams), hipMemcpyDeviceToHost) != hipSuccess) rc = -1;
+    if (rc == 0) {
+        const uint32_t a = r.active == dl0.d ? 0u : r.active == dl1.d ? 1u : 2u;
+        const uint32_t nx = r.next_active == dl0.d ? 0u : r.next_active == dl1.d ? 1u : 2u;
+        dq.finish(rc);
+        const uint32_t w[KAT_PARAMS_OUT] = {r.per_sample, r.chunk, r.round, r.cpp, r.u_cpp.d, r.u_cpp.m, r.u_cpp.s1, r.u_cpp.s2,
+                                            r.n_items, r.fine_base, r.fine_px, r.claim, r.claim_fine, r.round_base,
+                                            r.seg_base, r.seg_n, a, nx, q, 0u, 0u, 0u, 0u, 0u};
+        for (int k = 0; k < KAT_PARAMS_OUT; k++) out[k] = w[k];
+    }
+    dcounts.finish(rc); dcnt.finish(rc); dh.finish(rc); dl0.finish(rc); dl1.finish(rc); dq.finish(rc);
+    (void)hipFree(dP);
+    delete[] counts;
+    return rc;
+}
+int kat_pixel_claim_consts(int which) { return which == 0 ? (int)GS_CLAIM_DIV : which == 1 ? (int)GS_CLAIM_FINE : which == 2 ? (int)GS_ROUND_WHOLE_MAX_BATCH : -1; }
+
+// gs_round_combine_kernel (fold 0; fold 2: the same with per_sample 0, a whole-batch round, which the
+// kernel must leave alone) or gs_round_fold_kernel (fold 1) of round `round` over grid blocks: the
+// segment active[seg_base, seg_base + seg_n) of a list of n_active entries; partial
+// seg_n * bs * 3 doubles (sample-major); pstate (capacity * 5), pbatches (capacity; fold only),
+// next_active (capacity entries), next_count (round_counts[round + 1]) and pix (counters[C_PIX];
+// null: the kernel runs without counters) are in/out.
+int kat_pixel_round_step(const KatPixelLayout* L, int fold, uint32_t round, uint32_t grid, const uint32_t* active,
+                         uint32_t n_active, uint32_t seg_base, uint32_t seg_n, const double* partial, uint64_t n_partial,
+                         double* pstate, uint32_t* pbatches, uint32_t* next_active, uint32_t* next_count,
+                         unsigned long long* pix) {
+    PxCtx c;
+    if (grid < 1 || grid > 65536u || fold < 0 || fold > 2 || round > 4096u || !active || !partial || !pstate ||
+        !next_active || !next_count || (fold == 1 && !pbatches) || !L)
+        return -2;
+    if (GS_ROUND_PIXEL_MAJOR != 0) return -2;  // (the cases are written for the sample-major layout)
+    if (n_active < 1 || (uint64_t)seg_base + seg_n > n_active || (uint64_t)(round + 1u) * L->bs > (1ull << 53)) return -2;
+    if (n_partial < (uint64_t)seg_n * L->bs * 3 || n_partial < 3) return -2;
+    int rc = px_begin(L, c);
+    if (rc) return rc;
+    bool ok = n_active <= c.cap && (uint64_t)*next_count + seg_n <= c.cap;
+    for (uint32_t k = 0; ok && k < n_active; k++)  // (an active pixel is real: `direct` takes its image index)
+        ok = active[k] < c.cap && px_real(L, L->order, active[k]);
+    if (!ok) { (void)px_end(c, false); return -2; }
+    PxBuf<uint32_t> dact(const_cast<uint32_t*>(active), n_active, false);
+    PxBuf<double> dp(const_cast<double*>(partial), (size_t)n_partial, false);
+    PxBuf<double> ds(pstate, (size_t)c.cap * 5, true);
+    PxBuf<uint32_t> db(pbatches, c.cap, true);
+    PxBuf<uint32_t> dn(next_active, c.cap, true);
+    uint32_t* counts = new uint32_t[(size_t)round + 2]();
+    counts[round] = n_active;
+    counts[round + 1] = *next_count;
+    PxBuf<uint32_t> dcounts(counts, (size_t)round + 2, true);
+    unsigned long long cnt[C_N] = {};
+    if (pix) cnt[C_PIX] = *pix;
+    PxBuf<unsigned long long> dcnt(pix ? cnt : nullptr, C_N, true);
+    c.kp.per_sample = fold == 2 ? 0u : 1u;
+    c.kp.seg_base = seg_base;
+    c.kp.seg_n = seg_n;
+    c.kp.round = round;
+    c.kp.round_base = round * L->bs;
+    c.kp.active = dact.d;
+    c.kp.next_active = dn.d;
+    c.kp.partial = dp.d;
+    c.kp.pstate = ds.d;
+    c.kp.pbatches = db.d;
+    c.kp.round_counts = dcounts.d;
+    c.kp.counters = dcnt.d;
+    KParams* dP = dcopy(&c.kp, 1);
+    ok = !dact.bad() && !dp.bad() && !ds.bad() && !db.bad() && !dn.bad() && !dcounts.bad() && !dcnt.bad() && dP;
+    if (ok) {
+        if (fold == 1) hipLaunchKernelGGL(gs_round_fold_kernel, dim3(grid), dim3(256), 0, 0, dP, round);
+        else hipLaunchKernelGGL(gs_round_combine_kernel, dim3(grid), dim3(256), 0, 0, dP, round);
+    }
+    rc = px_end(c);
+    if (!ok) rc = -1;
+    dact.finish(rc); dp.finish(rc); ds.finish(rc); db.finish(rc); dn.finish(rc); dcounts.finish(rc); dcnt.finish(rc);
+    if (rc == 0) {
+        *next_count = counts[round + 1];
+        if (pix) *pix = cnt[C_PIX];
+    }
+    (void)hipFree(dP);
+    delete[] counts;
+    return rc;
+}
+
+// gs_round_resolve_kernel over gs_accum_blocks(capacity) blocks.  pstate capacity * 5, pbatches
+// capacity; map_samples, map_error (capacity each; null: not asked for) and summary
+// (GS_ROUND_SUMMARY_WORDS; null: none) are in/out.
+int kat_pixel_round_resolve(const KatPixelLayout* L, const double* pstate, const uint32_t* pbatches,
+                            uint32_t* map_samples, float* map_error, unsigned long long* summary) {
+    PxCtx c;
+    if (!pstate || !pbatches) return -2;
+    int rc = px_begin(L, c);
+    if (rc) return rc;
+    PxBuf<double> ds(const_cast<double*>(pstate), (size_t)c.cap * 5, false);
+    PxBuf<uint32_t> db(const_cast<uint32_t*>(pbatches), c.cap, false);
+    PxBuf<uint32_t> dm(map_samples, c.cap, true);
+    PxBuf<float> de(map_error, c.cap, true);
+    PxBuf<unsigned long long> dsum(summary, GS_ROUND_SUMMARY_WORDS, true);
+    c.kp.pstate = ds.d;
+    c.kp.pbatches = db.d;
+    c.kp.map_samples = dm.d;
+    c.kp.map_error = de.d;
+    c.kp.round_summary = dsum.d;
+    KParams* dP = dcopy(&c.kp, 1);
+    const bool ok = !ds.bad() && !db.bad() && !dm.bad() && !de.bad() && !dsum.bad() && dP;
+    if (ok) hipLaunchKernelGGL(gs_round_resolve_kernel, dim3(gs_accum_blocks(c.cap)), dim3(256), 0, 0, dP);
+    rc = px_end(c);
+    if (!ok) rc = -1;
+    ds.finish(rc); db.finish(rc); dm.finish(rc); de.finish(rc); dsum.finish(rc);
+    (void)hipFree(dP);
     return rc;
 }
 

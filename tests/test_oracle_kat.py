@@ -354,3 +354,57 @@ def test_hit_triangle_behind_the_origin_is_accepted():
     assert a["t"][1] == 2.0 and a["t"][2] == -2.0
     assert a["u"][2] == 0.25 and a["v"][2] == 0.25 and a["mat"][2] == m[2]
     assert tuple(a["p"][2]) == (0.25, 0.25, -2.0) and list(a["tri_tests"]) == [1, 1, 1]
+
+
+# ------------------------------------------------------------------ camera.rs:125-171 (sample_fold)
+def _lum(c):
+    return 0.299 * c[0] + 0.587 * c[1] + 0.144 * c[2]  # color.rs:31-33, in its order
+
+
+def test_sample_fold_two_sample_batch_converges():
+    # batch 2, confidence 1, tolerance 1.  Samples (1, 1, 1) and (3, 3, 3): l1 = lum(1,1,1) ~ 1.03, l2 ~ 3.09.
+    # :137 sample_count = 2; :150 mean = (l1 + l2) / 2 ~ 2.06; :151 variance = 1 / (2 - 1) * (sq - sum * sum / 2)
+    # = (l1 - l2)^2 / 2 ~ 2.12; :153 convergence = 1 * 2.12 / 2 ~ 1.06 < mean^2 * 1 ~ 4.24: break at :157 after one
+    # batch, and :167 gives (1 + 3) / 2 = 2 per channel, exactly.
+    l1, l2 = _lum((1.0, 1.0, 1.0)), _lum((3.0, 3.0, 3.0))
+    s = np.array([[[1.0, 1.0, 1.0], [3.0, 3.0, 3.0], [9.0, 9.0, 9.0], [9.0, 9.0, 9.0]]])
+    a = oracle.sample_fold(s, 2, 1.0, 1.0, 100)
+    assert a["batches"][0] == 1 and a["reason"][0] == oracle.FOLD_CONVERGED
+    assert tuple(a["color"][0]) == (2.0, 2.0, 2.0)
+    assert tuple(a["sums"][0, 0]) == (4.0, 4.0, 4.0, l1 + l2, l1 * l1 + l2 * l2)
+    assert np.isnan(a["sums"][0, 1]).all()  # the second batch was never taken
+    # the same stream under a tolerance of 0.5: 1.06 < 4.24 * 0.25 = 1.06...: decided by the f64 values themselves
+    conv = 1.0 / (2.0 - 1.0) * ((l1 * l1 + l2 * l2) - (l1 + l2) * (l1 + l2) / 2.0) / 2.0
+    mean = (l1 + l2) / 2.0
+    b = oracle.sample_fold(s, 2, 1.0, 0.5, 100)
+    assert (b["batches"][0] == 1) == (conv < mean * mean * 0.25)
+
+
+def test_sample_fold_black_pixel_runs_to_max_samples():
+    # every sample black: sum = sq = 0, mean = 0, variance = 1 / (n - 1) * (0 - 0 / n) = 0, convergence = 0, and
+    # 0 < 0 * tol^2 = 0 is false for any tolerance (:156): only :162 ends the loop.  batch 4, max_samples 10:
+    # 4 > 10, 8 > 10 no; 12 > 10: three batches.  max_samples 8: 8 > 8 no, 12 > 8: three as well; 7: two.
+    s = np.zeros((3, 16, 3))
+    a = oracle.sample_fold(s, 4, 2.0, 1e30, [10, 8, 7])
+    assert list(a["batches"]) == [3, 3, 2] and list(a["reason"]) == [oracle.FOLD_MAX_SAMPLES] * 3
+    assert (a["color"] == 0.0).all() and not np.signbit(a["color"]).any()
+    assert (a["sums"][0, :3] == 0.0).all() and np.isnan(a["sums"][0, 3]).all()
+    # a stream shorter than the loop: reported, not read past
+    b = oracle.sample_fold(s[:1, :8], 4, 2.0, 1e30, 10)
+    assert b["batches"][0] == 2 and b["reason"][0] == oracle.FOLD_EXHAUSTED
+
+
+def test_sample_fold_batch_size_one_first_test_is_nan():
+    # batch 1: after the first sample sample_count - 1 = 0, so :151 is 1 / 0 * (l * l - l * l / 1) = inf * 0 = NaN,
+    # convergence is NaN and `NaN < x` is false whatever the tolerance (here 1e9): the pixel goes on unless :162
+    # stops it (1 > max_samples only for max_samples 0).  Second sample equal to the first: sum = 2 l, sq = 2 l^2
+    # (exact doublings), variance = 1 / 1 * (2 l^2 - 4 l^2 / 2) = 0, convergence 0 < mean^2 * tol^2: converged, two
+    # batches, colour = 2 c / 2 = c.
+    c = (0.25, 0.5, 0.75)
+    s = np.array([[c, c, c]] * 2)
+    a = oracle.sample_fold(s, 1, 1.0, 1e9, [5, 0])
+    assert list(a["batches"]) == [2, 1]
+    assert list(a["reason"]) == [oracle.FOLD_CONVERGED, oracle.FOLD_MAX_SAMPLES]
+    assert tuple(a["color"][0]) == c and tuple(a["color"][1]) == c
+    l = _lum(c)
+    assert tuple(a["sums"][0, 1]) == (0.5, 1.0, 1.5, l + l, l * l + l * l)
