@@ -280,6 +280,7 @@ SIGNATURES = {
     "gs_debug_set_cube_lists": (C.c_int32, [C.c_int32]),
     "gs_debug_set_cert_boxes": (C.c_int32, [C.c_int32]),
     "gs_debug_set_mirror_budget": (C.c_int32, [C.c_int64]),
+    "gs_debug_set_max_blocks": (C.c_int32, [C.c_int32]),
     "gs_debug_record_visits": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,
                                            C.POINTER(gs_partition), _P, _P, _P]),
     "gs_debug_last_launch_feat": (C.c_int32, [_P, C.POINTER(C.c_int32)]),

@@ -466,8 +466,21 @@ __host__ __device__ constexpr uint32_t nest_save_lds(int feat) {
                ? ((feat & GS_FEAT_GENERAL) ? 8u : 7u)
                : 0u;
 }
+// The fixed-spp sphere-leaf kernels (GS_FEAT_FIXED && GS_FEAT_SPHLEAF, their views and split-round
+// forms included: C1, C2, C4) keep the whole lane state in registers instead: three colour sums
+// and five words, touched once per sample or per item, fit the VGPRs those instantiations leave
+// idle under the 4-waves/SIMD cap (<468>: 104 of 128), and their 48 KiB of LDS go to the mirror,
+// which is read at every node step.  `feat` is the launched instantiation's own word (the host:
+// kernel_feat), not the scene's: the loop's kernel of the same scene keeps the LDS layout.
+#ifndef GS_LANE_REGS
+#define GS_LANE_REGS 1  // (A/B: 0 keeps every kernel's lane state in LDS)
+#endif
+__host__ __device__ constexpr bool lane_state_in_regs(int feat) {
+    return GS_LANE_REGS && (feat & GS_FEAT_FIXED) != 0 && (feat & GS_FEAT_SPHLEAF) != 0 &&
+           (feat & (GS_FEAT_MEDIA | GS_FEAT_NESTED | GS_FEAT_GENERAL | GS_FEAT_VISITS)) == 0;
+}
 __host__ __device__ constexpr uint32_t lane_nd(bool chunked, int feat) {
-    return (chunked ? (uint32_t)L_ND_CHUNKED : (uint32_t)L_ND) + (t_in_lds(feat) ? 3u : 0u);
+    return lane_state_in_regs(feat) ? 0u : (chunked ? (uint32_t)L_ND_CHUNKED : (uint32_t)L_ND) + (t_in_lds(feat) ? 3u : 0u);
 }
 // ... and the hit primitive's ref (written by leaf tests, read by the shade pass) in one
 // more u32 field, L_HREF.
@@ -479,7 +492,9 @@ __host__ __device__ constexpr bool ninst_in_lds(int feat) {
     return (feat & GS_FEAT_NESTED) != 0 && (feat & GS_FEAT_VISITS) == 0;
 }
 __host__ __device__ constexpr uint32_t lane_ninst(int feat) { return (uint32_t)L_NI + (t_in_lds(feat) ? 1u : 0u); }
-__host__ __device__ constexpr uint32_t lane_ni(int feat) { return lane_ninst(feat) + (ninst_in_lds(feat) ? 1u : 0u); }
+__host__ __device__ constexpr uint32_t lane_ni(int feat) {
+    return lane_state_in_regs(feat) ? 0u : lane_ninst(feat) + (ninst_in_lds(feat) ? 1u : 0u);
+}
 __host__ __device__ constexpr size_t lane_lds_bytes(bool chunked, int feat, uint32_t nsave = 0) {
     return (size_t)GS_BLOCK * ((lane_nd(chunked, feat) + nsave) * 8 + lane_ni(feat) * 4) + 128 + GS_STAMP_LDS;
 }

@@ -6,6 +6,9 @@
 
 // The instantiation for a feature set (gs_render_kernel<0> when there is none for it).
 void (*kernel_for(int feat))(KArgs);
+// That instantiation's own feature word (0 for the fallback; `feat` itself where kernel_for gives
+// null): what its lane-state layout follows (kernel_abi.hpp: lane_nd, lane_ni, lane_lds_bytes).
+int kernel_feat(int feat);
 // A split batch round may take the (feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT) instantiation.
 bool has_rsplit(int feat);
 // A views launch may take the (feat | GS_FEAT_FIXED | GS_FEAT_VIEWS) instantiation (for such a

@@ -257,7 +257,8 @@ __global__ __launch_bounds__(GS_BLOCK, GS_MIN_WAVES) void gs_render_kernel(KArgs
     }
     uint8_t* s_cubes = s_quads + (size_t)A.lds_quads * sizeof(TQuad);
     const QuadSrc qs{s_quads, A.tquads, A.lds_quads, s_cubes, A.lds_cubes};
-    // Per-lane pixel / path state after the mirror: [L_ND][GS_BLOCK] f64, [L_NI][GS_BLOCK] u32.
+    // Per-lane pixel / path state after the mirror: [L_ND][GS_BLOCK] f64, [L_NI][GS_BLOCK] u32
+    // (none of either in lane_state_in_regs kernels: the counters follow the mirror).
     double* s_d = (double*)(s_cubes + (size_t)A.lds_cubes * (GS_CUBE_DOUBLES * 8));
     uint32_t* s_i = (uint32_t*)(s_d + A.lane_nd * GS_BLOCK);
     unsigned long long* s_cnt = (unsigned long long*)(s_i + lane_ni(FEAT) * GS_BLOCK);
@@ -291,8 +292,13 @@ __global__ __launch_bounds__(GS_BLOCK, GS_MIN_WAVES) void gs_render_kernel(KArgs
     // claim block's bounds test and L_PIX are the tall frame's.
     constexpr bool kViews = (FEAT & GS_FEAT_VIEWS) != 0;
     // (t_in_lds kernels: the throughput's three fields first, at fixed offsets)
-#define LD(k) s_d[((k) + (t_in_lds(FEAT) ? 3 : 0)) * GS_BLOCK + tid]
-#define LI(k) s_i[(k) * GS_BLOCK + tid]
+    // (lane_state_in_regs kernels: per-lane locals instead -- every index is a constant, so
+    // the fields are plain VGPRs, and the ones a kernel never reads cost nothing)
+    constexpr bool kLaneRegs = lane_state_in_regs(FEAT);
+    double r_d[L_ND] = {};
+    uint32_t r_i[L_NI] = {};
+#define LD(k) (*(kLaneRegs ? &r_d[(k)] : &s_d[((k) + (t_in_lds(FEAT) ? 3 : 0)) * GS_BLOCK + tid]))
+#define LI(k) (*(kLaneRegs ? &r_i[(k)] : &s_i[(k) * GS_BLOCK + tid]))
     if constexpr (kSphLeaf) LI(L_HINST) = GS_REF_NONE;
     // GS_FEAT_NESTED: the instance chain whose BVH the lane walks (GS_REF_NONE: the top level)
     constexpr bool kNested = (FEAT & GS_FEAT_NESTED) != 0;
@@ -1473,6 +1479,16 @@ void (*kernel_for(int feat))(KArgs) {
 #undef GS_K0
 #undef GS_KR
 #undef GS_K
+#endif
+}
+// The feature word of the instantiation kernel_for(feat) returns: every line of its table maps a
+// word to that word's own instantiation, and every other word to the fallback (or to none).
+int kernel_feat(int feat) {
+#ifdef GS_ONLY_FEAT
+    (void)feat;
+    return GS_ONLY_FEAT;
+#else
+    return kernel_for(feat) == kernel_for(0) ? 0 : feat;
 #endif
 }
 // A split batch round may take the (F | FIXED | RSPLIT) instantiation (kernel_for's GS_KR list).

@@ -49,6 +49,7 @@ static const uint64_t kMaxRounds = 1u << 16;  // more batches than this: the per
 static std::atomic<int32_t> g_cube_lists{1};  // gs_debug_set_cube_lists
 static std::atomic<int32_t> g_cert_boxes{1};  // gs_debug_set_cert_boxes
 static std::atomic<int64_t> g_mirror_budget{-1};  // gs_debug_set_mirror_budget
+static std::atomic<int32_t> g_max_blocks{0};  // gs_debug_set_max_blocks: 0 = no limit of its own
 
 Knobs read_knobs() {
     const auto rlx = std::memory_order_relaxed;
@@ -67,6 +68,7 @@ Knobs read_knobs() {
     k.cube_lists = g_cube_lists.load(rlx);
     k.cert_boxes = g_cert_boxes.load(rlx);
     k.mirror_budget = g_mirror_budget.load(rlx);
+    k.max_blocks = g_max_blocks.load(rlx);
     return k;
 }
 
@@ -142,6 +144,12 @@ gs_status gs_debug_set_cert_boxes(int32_t on) {
 gs_status gs_debug_set_mirror_budget(int64_t bytes) {
     if (bytes < -1) return fail(GS_ERR_ARG, "the mirror budget is -1 (the block's own) or a byte count >= 0");
     g_mirror_budget = bytes;
+    return GS_OK;
+}
+
+gs_status gs_debug_set_max_blocks(int32_t blocks) {
+    if (blocks < 0) return fail(GS_ERR_ARG, "the block limit is 0 (none) or a count >= 1");
+    g_max_blocks = blocks;
     return GS_OK;
 }
 
@@ -746,42 +754,83 @@ extern "C" uint32_t gs_views_chunk(const gs_device_scene* ds, const gs_camera* c
 }
 
 // ---------------------------------------------------------------- the launch shape
-// The launch shape for one lane-state layout (gs_device_scene::lcfg): the mirror takes what
-// the block's LDS limit leaves after the kernel's static LDS and the lane state (any prefix
-// of either record array is a valid mirror).
-static gs_status fit_mirror(gs_device_scene* ds, int dev, bool chunked) {
-    gs_device_scene::LaunchCfg& lc = ds->lcfg[chunked ? 1 : 0];
+// The launch shape of one instantiation (gs_device_scene::lcfg; lc.want, lc.views_round and
+// lc.chunked say which): the mirror takes what the block's LDS limit leaves after the launched
+// kernel's static LDS and its lane state (any prefix of either record array is a valid mirror).
+// The lane state is the launched kernel's own -- none in LDS for the fixed-spp sphere-leaf
+// kernels (lane_state_in_regs), while the loop's kernel of the same scene keeps its fields
+// there -- so the static-LDS check, the lane bytes and the occupancy all ask that kernel.
+static gs_status fit_mirror(gs_device_scene* ds, int dev, gs_device_scene::LaunchCfg& lc) {
     HIPCHK(hipDeviceGetAttribute(&ds->cus, hipDeviceAttributeMultiprocessorCount, dev));
-    hipFuncAttributes fa{};
-    HIPCHK(hipFuncGetAttributes(&fa, (const void*)kernel_for(ds->feat)));
     int max_lds = 0;
     HIPCHK(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-    // The node mirror must start at LDS address 0 (load_tnode): no static LDS.
-    if (fa.sharedSizeBytes != 0) return fail(GS_ERR_UNSUPPORTED, "render kernel with static LDS");
-    MirrorPrefix m = ds->mirror;
-    // (the nested walk's save slots too, when they displace no mirror record; else they
-    // stay in global memory: final_scene, whose mirror wants more than the 24 KiB the
-    // slots would leave, lost 5% with them in LDS -- profiles/r06/ab_nest_save_lds.txt)
-    uint32_t nsave = nest_save_lds(ds->feat);
-    if ((int64_t)max_lds - (int64_t)lane_lds_bytes(chunked, ds->feat, nsave) < m.bytes()) nsave = 0;
-    const int64_t room = (int64_t)max_lds - (int64_t)lane_lds_bytes(chunked, ds->feat, nsave);
-    if (room < 0) return fail(GS_ERR_UNSUPPORTED, "lane state exceeds the device's LDS per block");
-    // shrink the least valuable prefix first: cubes, quads, then all
-    while (m.bytes() > room && m.cubes) m.cubes = m.cubes - 1 - m.cubes / 16;
-    while (m.bytes() > room && m.quads) m.quads = m.quads - 1 - m.quads / 16;
-    while (m.bytes() > room) {
-        if (m.nodes) m.nodes = m.nodes - 1 - m.nodes / 16;  // shrink the prefixes until they fit
-        if (m.leaves) m.leaves = m.leaves - 1 - m.leaves / 16;
+    const bool chunked = lc.chunked;
+    // (a views round's table has exact entries only: the word is the instantiation's own)
+    auto kernel = [&](int f) { return lc.views_round ? views_round_kernel_for(f) : kernel_for(f); };
+    auto own_feat = [&](int f) { return lc.views_round ? f : kernel_feat(f); };
+    // Without GS_FEAT_LDSTREE the launch takes another instantiation: fitted again should that
+    // one's lane state differ (none of the product kernels' does: the layout ignores the flag).
+    for (int f = lc.want;;) {
+        void (*kn)(KArgs) = kernel(f);
+        if (!kn) return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's round kernel in this build");
+        const int kf = own_feat(f);
+        hipFuncAttributes fa{};
+        HIPCHK(hipFuncGetAttributes(&fa, (const void*)kn));
+        // The node mirror must start at LDS address 0 (load_tnode): no static LDS.
+        if (fa.sharedSizeBytes != 0) return fail(GS_ERR_UNSUPPORTED, "render kernel with static LDS");
+        MirrorPrefix m = ds->mirror;
+        // (the nested walk's save slots too, when they displace no mirror record; else they
+        // stay in global memory: final_scene, whose mirror wants more than the 24 KiB the
+        // slots would leave, lost 5% with them in LDS -- profiles/r06/ab_nest_save_lds.txt)
+        uint32_t nsave = nest_save_lds(kf);
+        if ((int64_t)max_lds - (int64_t)lane_lds_bytes(chunked, kf, nsave) < m.bytes()) nsave = 0;
+        const int64_t room = (int64_t)max_lds - (int64_t)lane_lds_bytes(chunked, kf, nsave);
+        if (room < 0) return fail(GS_ERR_UNSUPPORTED, "lane state exceeds the device's LDS per block");
+        // shrink the least valuable prefix first: cubes, quads, then all
+        while (m.bytes() > room && m.cubes) m.cubes = m.cubes - 1 - m.cubes / 16;
+        while (m.bytes() > room && m.quads) m.quads = m.quads - 1 - m.quads / 16;
+        while (m.bytes() > room) {
+            if (m.nodes) m.nodes = m.nodes - 1 - m.nodes / 16;  // shrink the prefixes until they fit
+            if (m.leaves) m.leaves = m.leaves - 1 - m.leaves / 16;
+        }
+        int f2 = f;
+        if (m.nodes < ds->node_records || m.leaves < ds->leaf_records) f2 &= ~GS_FEAT_LDSTREE;
+        if (f2 != f && kernel(f2) &&
+            (lane_lds_bytes(chunked, own_feat(f2), nest_save_lds(own_feat(f2))) != lane_lds_bytes(chunked, kf, nest_save_lds(kf)))) {
+            f = f2;
+            continue;
+        }
+        lc.mirror = m;
+        lc.lds = lane_lds_bytes(chunked, kf, nsave) + (size_t)m.bytes();
+        lc.nest_lds = nsave;
+        lc.lane_nd = lane_nd(chunked, kf) + nsave;
+        lc.feat = f2;
+        break;
     }
-    lc.mirror = m;
-    lc.lds = lane_lds_bytes(chunked, ds->feat, nsave) + (size_t)m.bytes();
-    lc.nest_lds = nsave;
-    lc.feat = ds->feat;
-    if (m.nodes < ds->node_records || m.leaves < ds->leaf_records) lc.feat &= ~GS_FEAT_LDSTREE;
+    void (*kn)(KArgs) = kernel(lc.feat);
+    if (!kn) return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's round kernel in this build");
     int occ = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kernel_for(lc.feat), GS_BLOCK, lc.lds));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)kn, GS_BLOCK, lc.lds));
     lc.per_cu = occ < 1 ? 1 : (occ > 8 ? 8 : occ);
-    lc.ready = true;
+    return GS_OK;
+}
+
+// The shape for a launch of `want` (cached per scene; the caller holds the scene's mutex).
+static gs_status launch_shape(gs_device_scene* ds, int dev, int want, bool views_round, bool chunked,
+                              const gs_device_scene::LaunchCfg** out) {
+    for (const auto& c : ds->lcfg)
+        if (c.want == want && c.views_round == views_round && c.chunked == chunked) {
+            *out = &c;
+            return GS_OK;
+        }
+    gs_device_scene::LaunchCfg lc;
+    lc.want = want;
+    lc.views_round = views_round;
+    lc.chunked = chunked;
+    gs_status e = fit_mirror(ds, dev, lc);
+    if (e != GS_OK) return e;
+    ds->lcfg.push_back(lc);
+    *out = &ds->lcfg.back();
     return GS_OK;
 }
 
@@ -854,7 +903,7 @@ static KParams fill_params(const gs_device_scene* ds, const LaunchReq& q, const 
 }
 
 // The hot kernel arguments (P: the slot's parameter block, set by the caller).
-static KArgs fill_args(const gs_device_scene* ds, const gs_device_scene::LaunchCfg& lc, bool chunked, const Knobs& k) {
+static KArgs fill_args(const gs_device_scene* ds, const gs_device_scene::LaunchCfg& lc, const Knobs& k) {
     KArgs a{};
     a.tnodes = ds->dev.tnodes;
     a.tboxes = ds->dev.tboxes;
@@ -871,7 +920,7 @@ static KArgs fill_args(const gs_device_scene* ds, const gs_device_scene::LaunchC
     a.lds_quads = lc.mirror.quads;
     a.lds_cubes = lc.mirror.cubes;
     a.cubes = ds->dev.cubes;
-    a.lane_nd = lane_nd(chunked, ds->feat) + lc.nest_lds;
+    a.lane_nd = lc.lane_nd;
     a.nest_lds = lc.nest_lds;
     return a;
 }
@@ -955,12 +1004,40 @@ static gs_status bind_slot(LaunchSlot& sl, hipStream_t st, const WorkPlan& w, in
 #ifndef GS_USE_FIXED
 #define GS_USE_FIXED 1  // (A/B: 0 launches the generic instantiation for fixed-spp frames too)
 #endif
+// The instantiation a launch asks for, from the scene's feature set `sf` (the shape then drops
+// GS_FEAT_LDSTREE where the mirror is a strict prefix, fit_mirror).  It is chosen before the shape,
+// because the shape follows it: the lane state, and with it the mirror, differs between a scene's
+// loop kernel and its fixed-spp forms.
+static int launch_word(int sf, const WorkPlan& w, const Knobs& k, const LaunchReq& r, bool round_pass, bool views) {
+    if (round_pass) {
+        // A progressive adaptive pass: always split items; paths that always trace a camera ray
+        // take the fixed kernel's sample loop (GS_FEAT_RSPLIT).  (views: a views adaptation's pass,
+        // in the views form of the round's kernel -- every view's max_depth > 0 -- views_round_kernel_for)
+        const bool rsplit = GS_USE_RSPLIT && has_rsplit(sf) && r.cam->max_depth > 0;
+        return (rsplit ? sf | GS_FEAT_FIXED | GS_FEAT_RSPLIT : sf) | (views ? GS_FEAT_VIEWS : 0);
+    }
+    if (w.n_rounds) {
+        // Rounds whose items are surely split (gs_round_params_kernel: a requested chunk, a batch
+        // above GS_ROUND_WHOLE_MAX_BATCH, or whole-batch items off -- the default) and whose
+        // paths always trace a camera ray take the fixed kernel's sample loop too.
+        const bool rsplit = GS_USE_RSPLIT && has_rsplit(sf) && r.cam->max_depth > 0 &&
+                            (k.sample_chunk > 0 || r.ss->batch_size > GS_ROUND_WHOLE_MAX_BATCH || k.round_whole == 0);
+        return rsplit ? sf | GS_FEAT_FIXED | GS_FEAT_RSPLIT : sf;
+    }
+    // (a views launch: always chunked, every view's max_depth > 0 -- the fixed kernel's views form)
+    if (views) return sf | GS_FEAT_FIXED | GS_FEAT_VIEWS;
+    if (r.va) return GS_FEAT_PILOT;
+    // (a fixed-spp chunked launch takes the instantiation without the adaptive paths)
+    const bool fixed = GS_USE_FIXED && w.chunk != 0 && r.cam->max_depth > 0;
+    return sf | (fixed ? GS_FEAT_FIXED : 0);
+}
+
 // What the enqueue steps share: the stream, the grid and the timing events.
 struct Enqueue {
     hipStream_t st;
     unsigned blocks;
     size_t lds;
-    int feat;  // the launch shape's instantiation (LaunchCfg::feat)
+    int feat;  // the word to launch: the shape's instantiation (LaunchCfg::feat)
     hipEvent_t k_begin, k_end;
     const gs_device_scene* ds;
     // kernel_for(f), noted for gs_debug_last_launch_feat
@@ -987,12 +1064,7 @@ static gs_status enqueue_rounds(const Enqueue& q, const WorkPlan& w, const Knobs
     HIPCHK(launch_round_init_kernel(st, g_init, dP));
     if (q.k_begin) HIPCHK(hipEventRecord(q.k_begin, st));
     const unsigned g_comb = (unsigned)std::min<int64_t>((w.seg_px + 255) / 256, 8192);
-    // Rounds whose items are surely split (gs_round_params_kernel: a requested chunk, a batch
-    // above GS_ROUND_WHOLE_MAX_BATCH, or whole-batch items off -- the default) and whose
-    // paths always trace a camera ray take the fixed kernel's sample loop (GS_FEAT_RSPLIT).
-    const bool rsplit = GS_USE_RSPLIT && has_rsplit(q.feat) && r.cam->max_depth > 0 &&
-                        (k.sample_chunk > 0 || r.ss->batch_size > GS_ROUND_WHOLE_MAX_BATCH || k.round_whole == 0);
-    void (*rkern)(KArgs) = q.kernel(rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat);
+    void (*rkern)(KArgs) = q.kernel(q.feat);  // (launch_word: the split-round form where it applies)
     for (uint32_t rd = 0; rd < w.n_rounds; rd++)
         for (uint32_t sg = 0; sg < w.n_segs; sg++) {
             HIPCHK(launch_round_params_kernel(st, dP, rd, sg, w.seg_px, k.sample_chunk, k.round_whole));
@@ -1013,9 +1085,7 @@ static gs_status enqueue_rounds(const Enqueue& q, const WorkPlan& w, const Knobs
 static gs_status enqueue_round_pass(const Enqueue& q, const WorkPlan& w, const Knobs& k, const LaunchReq& r,
                                     const RoundArgs& ra, const KParams& kp, KParams* dP, const KArgs& a, bool views) {
     const hipStream_t st = q.st;
-    const bool rsplit = GS_USE_RSPLIT && has_rsplit(q.feat) && r.cam->max_depth > 0;
-    const int rfeat = (rsplit ? q.feat | GS_FEAT_FIXED | GS_FEAT_RSPLIT : q.feat) | (views ? GS_FEAT_VIEWS : 0);
-    void (*rkern)(KArgs) = views ? q.views_round_kernel(rfeat) : q.kernel(rfeat);
+    void (*rkern)(KArgs) = views ? q.views_round_kernel(q.feat) : q.kernel(q.feat);
     if (!rkern) return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's round kernel in this build");
     if (ra.first_round == 0 && ra.rounds) {
         const unsigned g_init = (unsigned)std::min<int64_t>(((int64_t)r.cap + 255) / 256, 8192);
@@ -1039,14 +1109,7 @@ static gs_status enqueue_round_pass(const Enqueue& q, const WorkPlan& w, const K
 static gs_status enqueue_frame(const Enqueue& q, const WorkPlan& w, const LaunchReq& r, const KParams* dP,
                                const KArgs& a, bool pass, bool views) {
     if (q.k_begin) HIPCHK(hipEventRecord(q.k_begin, q.st));
-    const bool pilot_kernel = r.va != nullptr;
-    // (a fixed-spp chunked launch takes the instantiation without the adaptive paths)
-    const bool fixed = GS_USE_FIXED && w.chunk != 0 && !w.n_rounds && r.cam->max_depth > 0;
-    // (a views launch: always chunked, every view's max_depth > 0 -- the fixed kernel's views form)
-    const int feat = views         ? q.feat | GS_FEAT_FIXED | GS_FEAT_VIEWS
-                     : pilot_kernel ? GS_FEAT_PILOT
-                                    : q.feat | (fixed ? GS_FEAT_FIXED : 0);
-    HIPCHK(launch_render_kernel(q.st, q.kernel(feat), q.blocks, q.lds, a));
+    HIPCHK(launch_render_kernel(q.st, q.kernel(q.feat), q.blocks, q.lds, a));
     if (q.k_end) HIPCHK(hipEventRecord(q.k_end, q.st));
     if (pass && views) {  // (a progressive views pass: one block per tile slot)
         HIPCHK(launch_views_accumulate_kernel(q.st, dP, r.cap / (uint32_t)(r.part->tile_w * r.part->tile_h)));
@@ -1110,18 +1173,22 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
     // the root and the mirror prefixes under it, pilot_end)
     gs_device_scene* mds = const_cast<gs_device_scene*>(ds);
     std::lock_guard<std::mutex> lock(mds->mu);
-    const bool chunked = w.chunk != 0;
-    gs_device_scene::LaunchCfg& lc = mds->lcfg[chunked ? 1 : 0];
-    if (!lc.ready) {
-        gs_status e = fit_mirror(mds, dev, chunked);
+    if (vw && !(ra ? has_views_rounds(ds->feat) : has_views(ds->feat)))
+        return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's kernel");
+    const gs_device_scene::LaunchCfg* lcp = nullptr;
+    {
+        const int want = launch_word(ds->feat, w, k, req, ra != nullptr, vw != nullptr);
+        gs_status e = launch_shape(mds, dev, want, ra && vw, w.chunk != 0, &lcp);
         if (e != GS_OK) return e;
     }
+    const gs_device_scene::LaunchCfg& lc = *lcp;
     const int per_cu = k.blocks_per_cu > 0 ? k.blocks_per_cu : lc.per_cu;
     int64_t blocks = (int64_t)ds->cus * per_cu;
     // no more waves than work: one lane per item at most (a round's items: at most one per sample)
     const int64_t max_blocks =
         ((int64_t)(w.n_rounds ? (uint64_t)w.seg_px * ss->batch_size : w.n_items(req.cap)) + GS_BLOCK - 1) / GS_BLOCK;
     if (blocks > max_blocks) blocks = max_blocks;
+    if (k.max_blocks > 0 && blocks > k.max_blocks) blocks = k.max_blocks;  // (test hook: lanes that run many items in turn)
     if (blocks < 1) blocks = 1;
     KParams kp = fill_params(ds, req, w, blocks);
     if (pass) {
@@ -1139,7 +1206,7 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
                                 : w.chunk  ? (size_t)kp.n_items * 3 * sizeof(double) : 0;
     LaunchSlot& sl = mds->slots[pick_slot(mds, st, need_partial)];
     if (sl.used && sl.stream != st) HIPCHK(hipStreamWaitEvent(st, sl.done, 0));
-    gs_status e = bind_slot(sl, st, w, lc.feat, blocks, need_partial, kp, ra == nullptr);
+    gs_status e = bind_slot(sl, st, w, ds->feat, blocks, need_partial, kp, ra == nullptr);
     if (e != GS_OK) return e;
     if (ra) {
         const GsRoundLayout l = gs_round_layout(req.cap, ra->R);
@@ -1155,8 +1222,6 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
         kp.map_error = ra->map_error;
     }
     if (vw) {  // the views' records into the slot's array, behind the slot's previous launch on the stream
-        if (!(ra ? has_views_rounds(lc.feat) : has_views(lc.feat)))
-            return fail(GS_ERR_UNSUPPORTED, "no views form of the scene's kernel");
         e = grow_buffer(sl, sl.views, sl.views_bytes, (size_t)vw->n * sizeof(gs_view), "views");
         if (e != GS_OK) return e;
         for (uint32_t first = 0; first < vw->n; first += GS_VIEW_BATCH) {
@@ -1188,7 +1253,7 @@ static gs_status launch(const gs_device_scene* ds, const gs_camera* cam, const g
         kp.order = sl.vorder;
         kp.vdelta = vw->d_vdelta;
     }
-    KArgs a = fill_args(ds, lc, chunked, k);
+    KArgs a = fill_args(ds, lc, k);
     a.P = sl.params;
     if (outs->item_visits) HIPCHK(hipMemsetAsync(outs->item_visits, 0, (size_t)cap * sizeof(uint32_t), st));
     HIPCHK(launch_params_kernel(st, kp, sl.params));  // (zeroes the queue)

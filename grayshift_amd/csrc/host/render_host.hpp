@@ -36,6 +36,7 @@ struct Knobs {
     int32_t cube_lists;      // gs_debug_set_cube_lists
     int32_t cert_boxes;      // gs_debug_set_cert_boxes: 1 the 1e15 rule decides, 0 no scene has certified boxes
     int64_t mirror_budget;   // gs_debug_set_mirror_budget: -1 the block's own budget, >= 0 at most this many bytes
+    int32_t max_blocks;      // gs_debug_set_max_blocks: 0 no limit, >= 1 at most this many blocks per launch
 };
 Knobs read_knobs();
 
@@ -139,16 +140,21 @@ struct gs_device_scene {
     // Launch state, mutated by launches of a const scene: guarded by `mu`.
     std::mutex mu;
     // launch geometry, computed at the first launch (host API queries cost ~0.5 ms each)
-    // Launch shape per lane-state layout ([1]: fixed-spp / chunked launches, [0]: adaptive):
-    // the mirror prefixes that fit next to that lane state, the dynamic LDS, the kernel
-    // instantiation (feat minus GS_FEAT_LDSTREE when the mirror is a strict prefix), blocks/CU.
+    // Launch shape per launched instantiation (`want`: the word the launch asks kernel_for or
+    // views_round_kernel_for for, e.g. feat | GS_FEAT_FIXED) and lane-state size (chunked: a
+    // fixed-spp launch, which keeps no Σlum / Σlum² / count): the mirror prefixes that fit next
+    // to that kernel's lane state, the dynamic LDS, the kernel's f64 lane fields (KArgs::lane_nd),
+    // the word to launch (`want` minus GS_FEAT_LDSTREE when the mirror is a strict prefix) and
+    // blocks/CU.  A few entries per scene at most; emptied when the placement changes.
     struct LaunchCfg {
-        bool ready = false;
+        int want = 0;
+        bool views_round = false, chunked = false;
         MirrorPrefix mirror;
-        uint32_t nest_lds = 0;
+        uint32_t nest_lds = 0, lane_nd = 0;
         size_t lds = 0;
         int feat = 0, per_cu = 0;
-    } lcfg[2];
+    };
+    std::vector<LaunchCfg> lcfg;
     int cus = 0;
     LaunchSlot slots[kLaunchSlots];
     uint32_t next_slot = 0;

@@ -17,16 +17,18 @@ namespace {
 
 // Bytes of threaded records mirrored in LDS per block (the most-tested ones): what is
 // left of the block's share of the CU's 160 KiB (4 waves/SIMD = 1024 lanes per CU) after
-// the lane state.  -1 = that budget; >= 0 explicit (A/B).
+// the lane state of the scene's fixed-spp kernel (none when that kernel keeps it in registers,
+// lane_state_in_regs).  -1 = that budget; >= 0 explicit (A/B).
 #ifndef GS_LDS_MIRROR
 #define GS_LDS_MIRROR -1
 #endif
 const int64_t g_lds_mirror = GS_LDS_MIRROR;  // (compile-time A/B only)
-int64_t lds_mirror_budget() {
+int64_t lds_mirror_budget(bool lane_regs) {
     const int64_t share = (int64_t)160 * 1024 * GS_BLOCK / (GS_MIN_WAVES * 4 * 64);  // the block's share of the CU
     // (sized for fixed-spp launches; an adaptive launch's larger lane state shrinks the
     // mirror's prefixes to fit at launch)
-    const int64_t left = share - (int64_t)GS_BLOCK * (L_ND_CHUNKED * 8 + L_NI * 4) - 1024;  // 1 KiB: static LDS + slack
+    const int64_t lane = lane_regs ? 0 : (int64_t)GS_BLOCK * (L_ND_CHUNKED * 8 + L_NI * 4);
+    const int64_t left = share - lane - 1024;  // 1 KiB: the block's counters + slack
     return left > 0 ? left : 0;
 }
 #ifndef GS_KIND_SHADE_BATCH
@@ -221,7 +223,7 @@ void adopt_placement(gs_device_scene* ds, Placed& pl) {
     ds->thr_root = pl.root;
     ds->mirror = pl.mirror;
     ds->pos = std::move(pl.pos);
-    ds->lcfg[0].ready = ds->lcfg[1].ready = false;  // mirror prefixes changed
+    ds->lcfg.clear();  // mirror prefixes changed
 }
 
 namespace {
@@ -951,8 +953,13 @@ gs_status gs_device_scene_create(const gs_flat_scene* s, gs_device_scene** out) 
     if (st != GS_OK) return st;
     score_nested_trees(t, n_top, a.insts, ds->nroot_rec);
 
-    ds->mirror_budget = g_lds_mirror < 0 ? lds_mirror_budget() : g_lds_mirror;
-    if (knobs.mirror_budget >= 0) ds->mirror_budget = std::min(knobs.mirror_budget, lds_mirror_budget());  // (test hook)
+    // (the placement's prefix is cut for the scene's fixed-spp kernel, whose lane-state layout
+    // follows from these facts alone -- choose_feat; the shading flags do not enter it)
+    const bool flat = !general && !nested && s->n_media == 0;
+    const int64_t own_budget = lds_mirror_budget(lane_state_in_regs(
+        GS_FEAT_FIXED | (flat ? 0 : GS_FEAT_GENERAL_KERNEL) | (flat && sphere_leaves_only(t, n_top) ? GS_FEAT_SPHLEAF : 0)));
+    ds->mirror_budget = g_lds_mirror < 0 ? own_budget : g_lds_mirror;
+    if (knobs.mirror_budget >= 0) ds->mirror_budget = std::min(knobs.mirror_budget, own_budget);  // (test hook)
     Placed pl = place_records(ds.get(), nullptr);
     if (pl.tnodes.size() >= (1u << 26) || pl.tleaves.size() >= (1u << 26))
         return fail(GS_ERR_UNSUPPORTED, "more than 2^26 top-level BVH records");

@@ -308,6 +308,13 @@ gs_status gs_debug_set_cert_boxes(int32_t on);
  * device. */
 gs_status gs_debug_set_mirror_budget(int64_t bytes);
 
+/* Test hook (additive: the ABI stays 11): at most this many blocks in a render-kernel launch
+ * (0, default: the device's CUs x blocks per CU, and no more lanes than work items).  With
+ * fewer lanes than items every lane runs many items in turn.  Scheduling only: every value
+ * renders the same bits and counters.  Negative values: GS_ERR_ARG.  Host only; callable
+ * without a device. */
+gs_status gs_debug_set_max_blocks(int32_t blocks);
+
 /* Test hook: the auto sample-chunk rule's budget for chunk sums (default 4 GiB; 0
  * restores it).  A smaller budget makes renders take the chunk-doubling branch. */
 gs_status gs_debug_set_partial_budget(uint64_t bytes);
