@@ -150,6 +150,22 @@ pub struct gs_view {
     pub cam: gs_camera, pub seed: u64,
 }
 
+/// A ray query's ray: origin, direction, time and the interval (additive, ABI 11).  72 B.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_ray {
+    pub o: [f64; 3], pub d: [f64; 3],
+    pub time: f64, pub tmin: f64, pub tmax: f64,
+}
+/// A ray query's record: t and HitRecord's fields, the hit's refs, the stream after.  104 B.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_ray_hit {
+    pub t: f64, pub p: [f64; 3], pub n: [f64; 3], pub u: f64, pub v: f64,
+    pub hit: u32, pub front: u32, pub material: u32, pub r#ref: u32, pub inst: u32, pub pad: u32,
+    pub state: u64,
+}
+pub const GS_QUERY_CLOSEST: i32 = 0;
+pub const GS_QUERY_ANY: i32 = 1;
+
 /// An open views accumulation of the frame context (progressive views; additive, ABI 11).
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct gs_views_accum_info {
@@ -254,6 +270,11 @@ extern "C" {
                               d_nodes: *mut gs_node, d_order: *mut u32, d_work: *mut c_void, work_bytes: i64,
                               stream: *mut c_void) -> gs_status;
     pub fn gs_bvh_build_status(d_work: *mut c_void, stream: *mut c_void) -> gs_status;
+    /// Ray queries: world.hit(ray, Interval, rec) for caller rays, closest or any hit (ABI 11).
+    pub fn gs_query_rays_async(scene: *const gs_device_scene, d_rays: *const gs_ray, n: i64, mode: i32, seed: u64,
+                               d_hits: *mut gs_ray_hit, d_counts: *mut u32, stream: *mut c_void) -> gs_status;
+    pub fn gs_query_rays(scene: *const gs_device_scene, rays: *const gs_ray, n: i64, mode: i32, seed: u64,
+                         hits: *mut gs_ray_hit, counts: *mut u32) -> gs_status;
     pub fn gs_ppm_max_bytes(width: i32, height: i32) -> i64;
     pub fn gs_ppm_scratch_bytes(width: i32, height: i32) -> i64;
     pub fn gs_ppm_encode_async(d_rgb8: *const u8, width: i32, height: i32, d_text: *mut c_char, text_capacity: i64,

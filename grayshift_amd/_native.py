@@ -236,6 +236,21 @@ class gs_view(C.Structure):
     _fields_ = [("cam", gs_camera), ("seed", C.c_uint64)]
 
 
+class gs_ray(C.Structure):
+    """A ray query's ray: origin, direction, time and the interval (tmin, tmax).  72 B."""
+    _fields_ = [("o", D3), ("d", D3), ("time", C.c_double), ("tmin", C.c_double), ("tmax", C.c_double)]
+
+
+class gs_ray_hit(C.Structure):
+    """A ray query's record: t and HitRecord's fields, the hit's refs, the stream after.  104 B."""
+    _fields_ = [("t", C.c_double), ("p", D3), ("n", D3), ("u", C.c_double), ("v", C.c_double),
+                ("hit", C.c_uint32), ("front", C.c_uint32), ("material", C.c_uint32), ("ref", C.c_uint32),
+                ("inst", C.c_uint32), ("pad", C.c_uint32), ("state", C.c_uint64)]
+
+
+GS_QUERY_CLOSEST, GS_QUERY_ANY = 0, 1
+
+
 class gs_views_accum_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_views", C.c_uint32), ("chunk", C.c_uint32),
                 ("passes", C.c_uint32), ("tile_h", C.c_int32), ("counters", gs_counters)]
@@ -319,6 +334,8 @@ SIGNATURES = {
     "gs_bvh_build_lds_members": (C.c_uint32, []),
     "gs_bvh_build_async": (C.c_int32, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_int64, _P]),
     "gs_bvh_build_status": (C.c_int32, [_P, _P]),
+    "gs_query_rays_async": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P, _P]),
+    "gs_query_rays": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P]),
     "gs_render": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64, _P,
                               C.POINTER(gs_stats)]),
     "gs_render_multi": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,

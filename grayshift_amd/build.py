@@ -1,7 +1,8 @@
 """Build the in-tree native libraries.
 
 * ``grayshift_amd/libgrayshift.so`` — the product: HIP megakernel for gfx950 plus
-  the C++ host mirror, one shared library (hipcc; no torch, no JIT cache).
+  the C++ host mirror, one shared library (hipcc; no torch, no JIT cache), and beside it
+  ``libgrayshift_query.so``, the ray-query kernels it loads.
 * ``oracle/liboracle.so`` — the CPU checker (test infrastructure; g++ via
   oracle/Makefile).
 
@@ -28,11 +29,28 @@ SOURCES = [
     os.path.join(HERE, "csrc", "device", "bvh_build.hip"),  # BVHNode::from_list on the device
     os.path.join(HERE, "csrc", "host", "scene.cpp"),      # flat scene -> device scene
     os.path.join(HERE, "csrc", "host", "launch.cpp"),     # device scene -> launches
+    os.path.join(HERE, "csrc", "host", "query.cpp"),      # ray queries: checks, the one launch
     os.path.join(HERE, "csrc", "host", "world.cpp"),
     os.path.join(HERE, "csrc", "host", "camera.cpp"),
     os.path.join(HERE, "csrc", "host", "host_capi.cpp"),
     os.path.join(HERE, "csrc", "host", "multi_gpu.cpp"),
 ]
+
+
+# The ray-query kernels (world.hit for caller rays) are a translation unit of their own, listed
+# beside bvh_build.hip, and are linked into a library of their own next to the product,
+# libgrayshift_query.so, which libgrayshift.so needs: the product's .hip_fatbin -- whose hash keys
+# the committed PMC and stamps summaries (grayshift_amd/codeobj.py) -- holds the megakernel's code
+# objects only, so adding or changing a query kernel leaves every render profile valid.
+QUERY_SOURCE = os.path.join(HERE, "csrc", "device", "query.hip")
+
+
+def query_lib(lib):
+    """The ray-query library that goes with a product library: <name>_query.so beside it."""
+    return lib[:-3] + "_query.so"
+
+
+QUERY_LIB = query_lib(LIB)
 
 
 def _headers():
@@ -63,12 +81,13 @@ def build_product(force=False, verbose=False, extra=(), out=None):
     or this file; `force` (and so every variant build) compiles them all."""
     lib = out or LIB
     headers = _headers()
-    if not force and not _stale(lib, SOURCES + headers):
+    qlib = query_lib(lib)
+    if not force and not _stale(lib, SOURCES + [QUERY_SOURCE] + headers) and os.path.exists(qlib):
         return lib
     objs = []
     compiled = False
     tag = "" if out is None else "_" + os.path.basename(out).replace(".so", "")
-    for src in SOURCES:
+    for src in SOURCES + [QUERY_SOURCE]:
         obj = os.path.join(HERE, "csrc", "_obj" + tag, os.path.basename(src) + ".o")
         objs.append(obj)
         if not force and not _stale(obj, [src] + headers):
@@ -93,14 +112,18 @@ def build_product(force=False, verbose=False, extra=(), out=None):
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
         compiled = True
-    if not compiled and not _stale(lib, objs):
+    if not compiled and not _stale(lib, objs) and os.path.exists(qlib):
         return lib
-    tmp = lib + ".tmp"
-    cmd = [HIPCC, "-shared", "--offload-arch=" + ARCH, "-o", tmp] + objs + ["-lpthread", "-ldl"]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    os.replace(tmp, lib)
+    # the query kernels' library first (found beside the product at load time: $ORIGIN), then the product
+    qobj = objs.pop()
+    for target, cmd in ((qlib, [qobj, "-Wl,-soname," + os.path.basename(qlib)]),
+                        (lib, objs + [qlib, "-Wl,-rpath,$ORIGIN", "-lpthread", "-ldl"])):
+        tmp = target + ".tmp"
+        cmd = [HIPCC, "-shared", "--offload-arch=" + ARCH, "-o", tmp] + cmd
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+        os.replace(tmp, target)
     return lib
 
 

@@ -1357,6 +1357,7 @@ static gs_status pilot_end(gs_device_scene* ds, PilotRun& pr) {
         std::lock_guard<std::mutex> lock(ds->mu);
         for (int k = 0; k < kLaunchSlots; k++)
             if (ds->slots[k].used) HIPCHK(hipEventSynchronize(ds->slots[k].done));
+        if (ds->query_used) HIPCHK(hipEventSynchronize(ds->query_done));  // (ray queries read the records too)
         HIPCHK(hipMemcpy(const_cast<TNode*>(ds->dev.tnodes), pl.tnodes.data(), pl.tnodes.size() * sizeof(TNode),
                          hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(const_cast<TBox*>(ds->dev.tboxes), pl.tboxes.data(), pl.tboxes.size() * sizeof(TBox),

@@ -158,6 +158,11 @@ struct gs_device_scene {
     int cus = 0;
     LaunchSlot slots[kLaunchSlots];
     uint32_t next_slot = 0;
+    // Ray queries (query.cpp) take no slot: the event after the last one, for the pilot's end and
+    // the scene's destruction to wait for, and that query's stream
+    hipEvent_t query_done = nullptr;
+    hipStream_t query_stream = nullptr;
+    bool query_used = false;
     // Placement of the threaded records (place_records): the static estimate until the
     // first launch, whose pilot (run_pilot) measures the visits and re-places them.
     ThreadedTree tree;

@@ -1043,6 +1043,10 @@ gs_status gs_device_scene_destroy(gs_device_scene* ds) {
         if (sl.vstate) (void)hipFree(sl.vstate);
         if (sl.vorder) (void)hipFree(sl.vorder);
     }
+    if (ds->query_done) {
+        if (ds->query_used) (void)hipEventSynchronize(ds->query_done);
+        (void)hipEventDestroy(ds->query_done);
+    }
     if (ds->mem) (void)hipFree(ds->mem);
     delete ds;
     return GS_OK;

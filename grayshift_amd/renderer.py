@@ -239,6 +239,14 @@ class MultiRenderer:
         res["counters"] = i.counters.as_dict()
         return res
 
+    def query(self):
+        """A RayQuery (grayshift_amd.query) over rank 0's device scene: no second upload.  Valid
+        while this context is open; the current device must be rank 0's, as for any launch."""
+        from .query import RayQuery
+        d = C.c_void_p()
+        N.check(N.lib.gs_multi_scene(self.handle, 0, C.byref(d)))
+        return RayQuery(None, _shared=d)
+
     def scene_info(self, rank=0):
         """gs_device_scene_info of the scene on rank `rank`'s device."""
         d = C.c_void_p()

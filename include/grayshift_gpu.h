@@ -989,6 +989,43 @@ gs_status gs_bvh_build_async(const double* d_boxes, const uint32_t* d_refs /* nu
                              int64_t work_bytes, void* stream);
 gs_status gs_bvh_build_status(void* d_work, void* stream); /* synchronises; GS_ERR_ARG on NaN */
 
+/* ---- Ray queries: world.hit(ray, Interval, rec) for caller rays (additive, ABI 11) ----
+ * What the reference answers with `world.hit(&ray, Interval::new(tmin, tmax), &mut rec)`
+ * (hittable.rs; BVH.rs:69-90 for the scene's tree), for a batch of rays in one launch of a kernel
+ * of its own: the same records in the same left-first order with the same open intervals, the
+ * triangle that ignores ray_t, and a ConstantMedium's draw taken inside the traversal.  Ray i's
+ * stream starts at stream_seed(seed, i, 0) and `state` is the stream after the walk,
+ * hit or miss.  GS_QUERY_CLOSEST walks to the end; GS_QUERY_ANY leaves at the first accepted hit
+ * (the same walk, draws and all, up to there), so its `hit` equals the closest query's.
+ *
+ * A hit: t, and HitRecord's fields at t -- p, n (against the ray), front, material (the flat
+ * scene's index), u, v -- with ref (the primitive or medium) and inst (the Translate / RotateY
+ * chain it was reached through, or GS_REF_NONE).  A miss: hit = 0, t = the tmax given, material =
+ * ref = inst = GS_REF_NONE, p, n, u, v all +0.0.  counts (nullable): the ray's own tests, uint32
+ * [n][8]: node visits, then sphere, moving-sphere, quad, triangle, instance, list and medium tests.
+ *
+ * Any ray bits are accepted (NaN, infinities, a zero direction, tmin > tmax): the answer is what
+ * the reference's arithmetic makes of them, and the walk ends after at most one visit per record.
+ * GS_ERR_ARG, before anything touches the device: a NULL scene, rays or hits; n < 0 or n >= 2^31;
+ * a mode other than the two.  n == 0 is GS_OK with no launch.  The async form takes device
+ * pointers and enqueues one launch on `stream`; it shares no buffer with the scene's renders and
+ * may overlap them on other streams.  The synchronous form takes host arrays. */
+typedef struct gs_ray {
+    double o[3], d[3];
+    double time, tmin, tmax;
+} gs_ray; /* 72 B */
+typedef struct gs_ray_hit {
+    double t, p[3], n[3], u, v;
+    uint32_t hit, front, material, ref, inst, pad;
+    uint64_t state;
+} gs_ray_hit; /* 104 B */
+#define GS_QUERY_CLOSEST 0
+#define GS_QUERY_ANY 1
+gs_status gs_query_rays_async(const gs_device_scene* scene, const gs_ray* d_rays, int64_t n, int32_t mode,
+                              uint64_t seed, gs_ray_hit* d_hits, uint32_t* d_counts /* nullable */, void* stream);
+gs_status gs_query_rays(const gs_device_scene* scene, const gs_ray* rays, int64_t n, int32_t mode, uint64_t seed,
+                        gs_ray_hit* hits, uint32_t* counts /* nullable */);
+
 /* Synchronous full-frame render on the current device: upload, render, copy back.
  * out_rgb: host buffer W*H*3 f32 (linear).  stats: host, nullable (counters, kernel and
  * render times, algorithmic bytes).  This is the one-call replacement for camera.rs:105-114:
