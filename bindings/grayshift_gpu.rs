@@ -163,6 +163,14 @@ pub struct gs_ray_hit {
     pub hit: u32, pub front: u32, pub material: u32, pub r#ref: u32, pub inst: u32, pub pad: u32,
     pub state: u64,
 }
+/// A radiance query's record: the sum of the ray's samples' colours (f64), its world.hit calls, the
+/// stream after its last sample (additive, ABI 11).  40 B.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_ray_radiance {
+    pub rgb: [f64; 3],
+    pub rays: u64,
+    pub state: u64,
+}
 pub const GS_QUERY_CLOSEST: i32 = 0;
 pub const GS_QUERY_ANY: i32 = 1;
 
@@ -275,6 +283,16 @@ extern "C" {
                                d_hits: *mut gs_ray_hit, d_counts: *mut u32, stream: *mut c_void) -> gs_status;
     pub fn gs_query_rays(scene: *const gs_device_scene, rays: *const gs_ray, n: i64, mode: i32, seed: u64,
                          hits: *mut gs_ray_hit, counts: *mut u32) -> gs_status;
+    /// Radiance queries: ray_color(ray, max_depth, world) for caller rays, `samples` of each (ABI 11).
+    pub fn gs_query_radiance_scratch_bytes(n: i64, samples: u32, chunk: u32) -> i64;
+    pub fn gs_debug_set_radiance_batch(shade_batch: i32) -> gs_status;
+    pub fn gs_query_radiance_async(scene: *const gs_device_scene, d_rays: *const gs_ray, n: i64, samples: u32,
+                                   chunk: u32, max_depth: u32, seed: u64, d_states: *const u64,
+                                   d_out: *mut gs_ray_radiance, d_counters: *mut gs_counters, d_scratch: *mut c_void,
+                                   scratch_bytes: i64, stream: *mut c_void) -> gs_status;
+    pub fn gs_query_radiance(scene: *const gs_device_scene, rays: *const gs_ray, n: i64, samples: u32, chunk: u32,
+                             max_depth: u32, seed: u64, states: *const u64, out: *mut gs_ray_radiance,
+                             counters: *mut gs_counters) -> gs_status;
     pub fn gs_ppm_max_bytes(width: i32, height: i32) -> i64;
     pub fn gs_ppm_scratch_bytes(width: i32, height: i32) -> i64;
     pub fn gs_ppm_encode_async(d_rgb8: *const u8, width: i32, height: i32, d_text: *mut c_char, text_capacity: i64,

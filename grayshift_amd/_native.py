@@ -251,6 +251,12 @@ class gs_ray_hit(C.Structure):
 GS_QUERY_CLOSEST, GS_QUERY_ANY = 0, 1
 
 
+class gs_ray_radiance(C.Structure):
+    """A radiance query's record: the sum of the ray's samples' colours, its world.hit calls, the
+    stream after its last sample.  40 B."""
+    _fields_ = [("rgb", D3), ("rays", C.c_uint64), ("state", C.c_uint64)]
+
+
 class gs_views_accum_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_views", C.c_uint32), ("chunk", C.c_uint32),
                 ("passes", C.c_uint32), ("tile_h", C.c_int32), ("counters", gs_counters)]
@@ -336,6 +342,11 @@ SIGNATURES = {
     "gs_bvh_build_status": (C.c_int32, [_P, _P]),
     "gs_query_rays_async": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P, _P]),
     "gs_query_rays": (C.c_int32, [_P, _P, C.c_int64, C.c_int32, C.c_uint64, _P, _P]),
+    "gs_query_radiance_scratch_bytes": (C.c_int64, [C.c_int64, C.c_uint32, C.c_uint32]),
+    "gs_debug_set_radiance_batch": (C.c_int32, [C.c_int32]),
+    "gs_query_radiance_async": (C.c_int32, [_P, _P, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P,
+                                            _P, _P, C.c_int64, _P]),
+    "gs_query_radiance": (C.c_int32, [_P, _P, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P]),
     "gs_render": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64, _P,
                               C.POINTER(gs_stats)]),
     "gs_render_multi": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,

@@ -43,6 +43,9 @@ SOURCES = [
 # the committed PMC and stamps summaries (grayshift_amd/codeobj.py) -- holds the megakernel's code
 # objects only, so adding or changing a query kernel leaves every render profile valid.
 QUERY_SOURCE = os.path.join(HERE, "csrc", "device", "query.hip")
+# ... and the radiance-query kernels (ray_color for caller rays), the same library's second unit
+RADIANCE_SOURCE = os.path.join(HERE, "csrc", "device", "radiance.hip")
+QUERY_SOURCES = [QUERY_SOURCE, RADIANCE_SOURCE]
 
 
 def query_lib(lib):
@@ -82,12 +85,12 @@ def build_product(force=False, verbose=False, extra=(), out=None):
     lib = out or LIB
     headers = _headers()
     qlib = query_lib(lib)
-    if not force and not _stale(lib, SOURCES + [QUERY_SOURCE] + headers) and os.path.exists(qlib):
+    if not force and not _stale(lib, SOURCES + QUERY_SOURCES + headers) and os.path.exists(qlib):
         return lib
     objs = []
     compiled = False
     tag = "" if out is None else "_" + os.path.basename(out).replace(".so", "")
-    for src in SOURCES + [QUERY_SOURCE]:
+    for src in SOURCES + QUERY_SOURCES:
         obj = os.path.join(HERE, "csrc", "_obj" + tag, os.path.basename(src) + ".o")
         objs.append(obj)
         if not force and not _stale(obj, [src] + headers):
@@ -115,8 +118,9 @@ def build_product(force=False, verbose=False, extra=(), out=None):
     if not compiled and not _stale(lib, objs) and os.path.exists(qlib):
         return lib
     # the query kernels' library first (found beside the product at load time: $ORIGIN), then the product
-    qobj = objs.pop()
-    for target, cmd in ((qlib, [qobj, "-Wl,-soname," + os.path.basename(qlib)]),
+    qobjs = objs[len(SOURCES):]
+    objs = objs[:len(SOURCES)]
+    for target, cmd in ((qlib, qobjs + ["-Wl,-soname," + os.path.basename(qlib)]),
                         (lib, objs + [qlib, "-Wl,-rpath,$ORIGIN", "-lpthread", "-ldl"])):
         tmp = target + ".tmp"
         cmd = [HIPCC, "-shared", "--offload-arch=" + ARCH, "-o", tmp] + cmd

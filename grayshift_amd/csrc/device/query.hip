@@ -4,10 +4,11 @@
 //
 // The megakernel's traversal cannot be lifted out of gs_render_kernel, but its two
 // ends are headers: the leaf stage (leaf.hpp: leaf_other, LeafHit) and the hit-record stage
-// (shading.hpp: reconstruct, HitRec).  gs_query_kernel runs its own plain walk between them, over
-// the threaded records the upload already makes (DevScene::tnodes / tboxes / tleaves / nroots): no
-// LDS mirror, no wave-level passes, no launch slot, no work queue.  Every node is decided by the
-// f64 slab test on its TBox, as AABB::hit decides it (box_hit_ref).  Its own translation unit, linked
+// (shading.hpp: reconstruct, HitRec).  gs_query_kernel runs a plain walk between them (query_walk.hpp,
+// shared with radiance.hip's kernel), over the threaded records the upload already makes
+// (DevScene::tnodes / tboxes / tleaves / nroots): no LDS mirror, no wave-level passes, no launch
+// slot, no work queue.  Every node is decided by the f64 slab test on its TBox, as AABB::hit
+// decides it (box_hit_ref).  Its own translation unit, linked
 // into a library of its own (build.py: libgrayshift_query.so), so nothing of render.hip, kernels.hpp,
 // the kernel table or the product's code objects changes with it.
 #include <hip/hip_runtime.h>
@@ -24,30 +25,11 @@ using namespace gsd;
 
 #include "leaf.hpp"
 #include "shading.hpp"
+#include "query_walk.hpp"
 
 namespace {
 
 constexpr int QUERY_THREADS = 256;
-
-// AABB::hit (AABB.rs:58-113) for a caller's interval, whose ends may be NaN: the updates are the
-// reference's own compare-and-assign (`if a > min { min = a }` keeps a NaN end, where geometry.hpp's
-// box_hit takes fmax, which is the same only while the ends are numbers -- as a render's always are).
-// The reference's early returns do not change the answer: once max <= min holds, later slabs only
-// raise min and lower max; with a NaN end no comparison with it ever holds.
-__device__ __forceinline__ void slab_ref(double mn, double mx, double o, double inv, double& lo, double& hi) {
-    const double t0 = (mn - o) * inv, t1 = (mx - o) * inv;
-    const bool s = t0 < t1;
-    const double a = s ? t0 : t1, b = s ? t1 : t0;
-    lo = a > lo ? a : lo;
-    hi = b < hi ? b : hi;
-}
-__device__ __forceinline__ bool box_hit_ref(const DNode& n, const d3& o, const d3& inv, double tmin, double tmax) {
-    double lo = tmin, hi = tmax;
-    slab_ref(n.mnx, n.mxx, o.x, inv.x, lo, hi);
-    slab_ref(n.mny, n.mxy, o.y, inv.y, lo, hi);
-    slab_ref(n.mnz, n.mxz, o.z, inv.z, lo, hi);
-    return !(hi <= lo);
-}
 
 __device__ __forceinline__ void chain_forward(const DevScene& sc, uint32_t cur, Ray& r) {
 #pragma unroll 1
@@ -70,7 +52,6 @@ template <int FEAT, bool ANY>
 __global__ __launch_bounds__(QUERY_THREADS) void gs_query_kernel(DevScene sc, const TQuad* tquads, uint32_t root,
                                                                 const gs_ray* rays, uint32_t n, uint64_t seed,
                                                                 gs_ray_hit* hits, uint32_t* counts) {
-    constexpr bool kNested = (FEAT & GS_FEAT_NESTED) != 0;
     constexpr bool kGeneral = (FEAT & GS_FEAT_GENERAL) != 0;
     __shared__ unsigned long long s_cnt[QUERY_THREADS * C_N];
     const size_t i = (size_t)blockIdx.x * QUERY_THREADS + threadIdx.x;
@@ -88,88 +69,14 @@ __global__ __launch_bounds__(QUERY_THREADS) void gs_query_kernel(DevScene sc, co
     uint64_t rng = stream_seed(seed, (uint32_t)i, (uint32_t)((uint64_t)i >> 32));
     const QuadSrc qs{nullptr, tquads, 0u, nullptr, 0u};  // no mirror: every record from global memory
 
-    Ray ray = ray0;            // the ray in the space of the tree being walked
-    d3 inv = inv_of(ray.d);    // AABB.rs:62: 1.0 / ray.direction, per axis
-    double a = len2(ray.d);    // sphere.rs:66
-    double closest = tmax;
-    bool hit = false;
-    uint32_t hit_ref = GS_REF_NONE, hit_inst = GS_REF_NONE, hit_outer = GS_REF_NONE;
-    uint32_t ninst = GS_REF_NONE;  // the instance leaf whose BVH the lane walks (none: the top level)
-    uint32_t ret = THR_END;        // ... and the link after that leaf
+    QWalk w;  // (query_walk.hpp: the walk both query kernels share)
+    qwalk_begin(w, ray0, root, tmax);
     uint32_t c_nodes = 0, c_sph = 0;
-    uint32_t cur = root;
-    // Termination for any ray bits (NaN or zero directions, tmin > tmax, infinities): a link only
-    // ever points forward in the tree's pre-order -- a node's hit link to the next record, its miss
-    // link past its subtree, a leaf's link to the next record -- so whatever the tests decide, each
-    // step moves on and the walk reaches THR_END after at most one visit per record.  A BVH under
-    // an instance chain is a second finite walk of the same kind, entered from the top level only
-    // (validate() allows one level), which returns to the saved forward link at THR_RET.  A
-    // malformed ray is a miss or whatever the reference's arithmetic makes of it, never a fault:
-    // no index is computed from the ray.
 #pragma unroll 1
-    while (cur != THR_END) {
-        if (kNested && cur == THR_RET) {  // the nested tree is done: back to the caller's ray
-            ray = ray0;
-            inv = inv_of(ray.d);
-            a = len2(ray.d);
-            cur = ret;
-            ninst = GS_REF_NONE;
-            continue;
-        }
-        if (cur < THR_END) {  // a node record: its byte offset
-            c_nodes++;
-            const size_t k = cur >> 5;
-            const auto b = sp<false>(sc.tboxes + k);
-            DNode nb;
-            nb.mnx = b->mnx; nb.mny = b->mny; nb.mnz = b->mnz;
-            nb.mxx = b->mxx; nb.mxy = b->mxy; nb.mxz = b->mxz;
-            const auto nd = sp<false>(sc.tnodes + k);
-            const uint32_t l_hit = nd->hit, l_miss = nd->miss;
-            cur = box_hit_ref(nb, ray.o, inv, tmin, closest) ? l_hit : l_miss;
-            continue;
-        }
-        const auto lf = sp<false>(sc.tleaves + (size_t)(cur & ~THR_LEAF));
-        const uint32_t next = lf->next, ref = lf->ref;
-        cur = next;
-        if ((ref >> GS_REF_SHIFT) == GS_REF_SPHERE) {  // a stationary sphere, inline in the record
-            c_sph++;
-            double t;
-            if (sphere_accept_rr(mk(lf->cx, lf->cy, lf->cz), lf->rr, ray, a, tmin, closest, t)) {
-                hit = true;
-                closest = t;
-                hit_ref = ref;
-                hit_inst = ninst;
-                hit_outer = GS_REF_NONE;
-                if (ANY) break;
-            }
-            continue;
-        }
-        Ray rl = ray;  // (the ray in the leaf's space after its instance chain)
-        const LeafHit lh = leaf_other<FEAT, false>(sc, qs, ref, rl, tmin, closest, rng, cnt);
-        if (lh.hit) {
-            hit = true;
-            closest = lh.t;
-            hit_ref = lh.ref;
-            if (kGeneral && lh.inst != GS_REF_NONE && ninst != GS_REF_NONE) {  // a chain inside a tree under a chain
-                hit_inst = lh.inst;
-                hit_outer = ninst;
-            } else {
-                hit_inst = (!kNested || lh.inst != GS_REF_NONE) ? lh.inst : ninst;
-                hit_outer = GS_REF_NONE;
-            }
-            if (ANY) break;
-        }
-        if (kNested && lh.enter != 0 && ninst == GS_REF_NONE) {
-            // the chain ended in a BVH: walked in this same loop with the ray in the tree's space
-            ret = next;
-            ninst = ref;
-            ray.o = rl.o;
-            ray.d = rl.d;
-            inv = inv_of(ray.d);
-            a = len2(ray.d);
-            cur = ld_u32<false>(sc.nroots + (lh.enter - 1u));
-        }
-    }
+    while (w.cur != THR_END) qwalk_step<FEAT, ANY>(sc, qs, w, ray0, tmin, rng, cnt, c_nodes, c_sph);
+    const bool hit = w.hit;
+    const double closest = w.closest;
+    const uint32_t hit_ref = w.hit_ref, hit_inst = w.hit_inst, hit_outer = w.hit_outer;
 
     // The record: HitRecord's fields from reconstruct of (ref, inst, t); one plain store per field.
     double o9[9];

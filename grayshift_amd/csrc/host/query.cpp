@@ -1,8 +1,10 @@
-// query.cpp — the host side of the ray queries (gs_query_rays_async, gs_query_rays): the argument
-// checks, the scene's mutex around the one launch, and the synchronous form's copies.  The kernel
-// and its instantiation table are csrc/device/query.hip's.
+// query.cpp — the host side of the ray queries (gs_query_rays_async, gs_query_rays) and the radiance
+// queries (gs_query_radiance_async, gs_query_radiance): the argument checks, the scratch sizing, the
+// scene's mutex around the launches, and the synchronous forms' copies.  The kernels and their
+// instantiation tables are csrc/device/query.hip's and radiance.hip's.
 #include <hip/hip_runtime_api.h>
 
+#include <atomic>
 #include <mutex>
 #include <string>
 
@@ -11,7 +13,27 @@
 hipError_t gs_query_launch(int feat, int any, const DevScene& sc, const TQuad* tquads, uint32_t root, const gs_ray* rays,
                            uint32_t n, uint64_t seed, gs_ray_hit* hits, uint32_t* counts, hipStream_t st);
 
+hipError_t gs_radiance_launch(int feat, const DevScene& sc, const TQuad* tquads, uint32_t root, const gs_ray* rays,
+                              uint32_t n, uint32_t samples, uint32_t chunk, uint32_t chunks, uint32_t max_depth,
+                              uint64_t seed, const uint64_t* states, gs_ray_radiance* out, gs_ray_radiance* part,
+                              unsigned long long* counters, uint32_t shade_batch, hipStream_t st);
+
 static_assert(sizeof(gs_ray) == 72 && sizeof(gs_ray_hit) == 104, "gs_ray / gs_ray_hit layout (grayshift_gpu.h)");
+static_assert(sizeof(gs_ray_radiance) == 40, "gs_ray_radiance layout (grayshift_gpu.h)");
+
+// Lanes of a wave that wait at their walk's end before the wave shades them (gs_debug_set_radiance_batch;
+// MI355X, C4's world: DESIGN.md §3.7).  Scheduling only: every choice returns the same bits.
+#define GS_RADIANCE_SHADE_BATCH 24
+static std::atomic<int32_t> g_radiance_batch{GS_RADIANCE_SHADE_BATCH};
+
+// A radiance query's chunking: `chunk` samples per work item (0: 16), chunks per ray; false when
+// the arguments are bad (n < 0, no samples, 2^31 items or more).
+static bool radiance_items(int64_t n, uint32_t samples, uint32_t chunk, uint32_t& chunk_out, uint32_t& chunks) {
+    if (n < 0 || samples == 0) return false;
+    chunk_out = chunk ? chunk : 16u;
+    chunks = (samples - 1u) / chunk_out + 1u;
+    return n < ((int64_t)1 << 31) && n * (int64_t)chunks < ((int64_t)1 << 31);
+}
 
 // The checks both forms share, on the arguments alone (nothing of the scene is read).
 static gs_status check_args(const char* who, const gs_device_scene* ds, const void* rays, int64_t n, int32_t mode,
@@ -76,6 +98,109 @@ gs_status gs_query_rays(const gs_device_scene* ds, const gs_ray* rays, int64_t n
     if (e != GS_OK) return e;
     if (h != hipSuccess) return fail(GS_ERR_HIP, std::string("gs_query_rays: ") + hipGetErrorString(h));
     if (f != hipSuccess) return fail(GS_ERR_HIP, std::string("gs_query_rays: hipFree: ") + hipGetErrorString(f));
+    return GS_OK;
+}
+
+gs_status gs_debug_set_radiance_batch(int32_t shade_batch) {
+    if (shade_batch < 0 || shade_batch > 64)
+        return fail(GS_ERR_ARG, "gs_debug_set_radiance_batch: shade_batch must be in [0, 64] (0: the default)");
+    g_radiance_batch.store(shade_batch ? shade_batch : GS_RADIANCE_SHADE_BATCH);
+    return GS_OK;
+}
+
+int64_t gs_query_radiance_scratch_bytes(int64_t n, uint32_t samples, uint32_t chunk) {
+    uint32_t c = 0, chunks = 0;
+    if (!radiance_items(n, samples, chunk, c, chunks)) return -1;
+    return chunks > 1u ? n * (int64_t)chunks * (int64_t)sizeof(gs_ray_radiance) : 0;
+}
+
+// The checks both radiance forms share, on the arguments alone (nothing of the scene is read).
+static gs_status check_radiance(const char* who, const gs_device_scene* ds, const void* rays, int64_t n, uint32_t samples,
+                                uint32_t chunk, const void* out, uint32_t& c, uint32_t& chunks) {
+    if (!ds || !rays || !out) return fail(GS_ERR_ARG, std::string(who) + ": null argument");
+    if (n < 0) return fail(GS_ERR_ARG, std::string(who) + ": n must not be negative");
+    if (samples == 0) return fail(GS_ERR_ARG, std::string(who) + ": samples must be at least 1");
+    if (!radiance_items(n, samples, chunk, c, chunks))
+        return fail(GS_ERR_ARG, std::string(who) + ": n * ceil(samples / chunk) must be below 2^31");
+    return GS_OK;
+}
+
+gs_status gs_query_radiance_async(const gs_device_scene* ds, const gs_ray* d_rays, int64_t n, uint32_t samples,
+                                  uint32_t chunk, uint32_t max_depth, uint64_t seed, const uint64_t* d_states,
+                                  gs_ray_radiance* d_out, gs_counters* d_counters, void* d_scratch, int64_t scratch_bytes,
+                                  void* stream) {
+    uint32_t c = 0, chunks = 0;
+    gs_status e = check_radiance("gs_query_radiance_async", ds, d_rays, n, samples, chunk, d_out, c, chunks);
+    if (e != GS_OK) return e;
+    const int64_t need = chunks > 1u ? n * (int64_t)chunks * (int64_t)sizeof(gs_ray_radiance) : 0;
+    if (need > 0 && (!d_scratch || scratch_bytes < need))
+        return fail(GS_ERR_ARG, "gs_query_radiance_async: scratch is null or smaller than gs_query_radiance_scratch_bytes");
+    if (n == 0) return GS_OK;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev != ds->device) return fail(GS_ERR_ARG, "scene lives on another device");
+    const hipStream_t st = (hipStream_t)stream;
+    gs_device_scene* mds = const_cast<gs_device_scene*>(ds);
+    // Under the scene's mutex with the ray queries' one event (gs_query_rays_async): the placement
+    // pilot's end waits for it before it rewrites the threaded records.
+    std::lock_guard<std::mutex> lock(mds->mu);
+    if (!mds->query_done) HIPCHK(hipEventCreateWithFlags(&mds->query_done, hipEventDisableTiming));
+    if (mds->query_used && mds->query_stream != st) HIPCHK(hipStreamWaitEvent(st, mds->query_done, 0));
+    HIPCHK(gs_radiance_launch(ds->feat, ds->dev, ds->tquads, ds->thr_root, d_rays, (uint32_t)n, samples, c, chunks,
+                              max_depth, seed, d_states, d_out, (gs_ray_radiance*)d_scratch,
+                              (unsigned long long*)d_counters, (uint32_t)g_radiance_batch.load(), st));
+    HIPCHK(hipEventRecord(mds->query_done, st));
+    mds->query_used = true;
+    mds->query_stream = st;
+    return GS_OK;
+}
+
+gs_status gs_query_radiance(const gs_device_scene* ds, const gs_ray* rays, int64_t n, uint32_t samples, uint32_t chunk,
+                            uint32_t max_depth, uint64_t seed, const uint64_t* states, gs_ray_radiance* out,
+                            gs_counters* counters) {
+    uint32_t c = 0, chunks = 0;
+    gs_status e = check_radiance("gs_query_radiance", ds, rays, n, samples, chunk, out, c, chunks);
+    if (e != GS_OK) return e;
+    if (n == 0) return GS_OK;
+    {  // (the last check, before the buffers are allocated: nothing is copied for a scene elsewhere)
+        int dev = 0;
+        HIPCHK(hipGetDevice(&dev));
+        if (dev != ds->device) return fail(GS_ERR_ARG, "scene lives on another device");
+    }
+    const size_t rb = (size_t)n * sizeof(gs_ray), sb = states ? (size_t)n * samples * 8 : 0;
+    const size_t ob = (size_t)n * sizeof(gs_ray_radiance), cb = counters ? sizeof(gs_counters) : 0;
+    const size_t pb = chunks > 1u ? (size_t)n * chunks * sizeof(gs_ray_radiance) : 0;
+    // one allocation: rays, states, out, counters, scratch (each a multiple of 8 B)
+    char* d = nullptr;
+    if (hipMalloc((void**)&d, rb + sb + ob + cb + pb) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(GS_ERR_OOM, "gs_query_radiance: hipMalloc of the ray and result buffers failed");
+    }
+    gs_ray* d_rays = (gs_ray*)d;
+    uint64_t* d_states = states ? (uint64_t*)(d + rb) : nullptr;
+    gs_ray_radiance* d_out = (gs_ray_radiance*)(d + rb + sb);
+    gs_counters* d_cnt = counters ? (gs_counters*)(d + rb + sb + ob) : nullptr;
+    void* d_part = pb ? (void*)(d + rb + sb + ob + cb) : nullptr;
+    gs_counters got = {};
+    hipError_t h = hipMemcpy(d_rays, rays, rb, hipMemcpyHostToDevice);
+    if (h == hipSuccess && states) h = hipMemcpy(d_states, states, sb, hipMemcpyHostToDevice);
+    if (h == hipSuccess && counters) h = hipMemset(d_cnt, 0, cb);
+    if (h == hipSuccess) {
+        e = gs_query_radiance_async(ds, d_rays, n, samples, chunk, max_depth, seed, d_states, d_out, d_cnt, d_part,
+                                    (int64_t)pb, nullptr);
+        if (e == GS_OK) h = hipStreamSynchronize(nullptr);
+        if (e == GS_OK && h == hipSuccess) h = hipMemcpy(out, d_out, ob, hipMemcpyDeviceToHost);
+        if (e == GS_OK && h == hipSuccess && counters) h = hipMemcpy(&got, d_cnt, cb, hipMemcpyDeviceToHost);
+    }
+    const hipError_t f = hipFree(d);
+    if (e != GS_OK) return e;
+    if (h != hipSuccess) return fail(GS_ERR_HIP, std::string("gs_query_radiance: ") + hipGetErrorString(h));
+    if (f != hipSuccess) return fail(GS_ERR_HIP, std::string("gs_query_radiance: hipFree: ") + hipGetErrorString(f));
+    if (counters) {  // accumulated into, as the device form
+        uint64_t* dst = reinterpret_cast<uint64_t*>(counters);
+        const uint64_t* src = reinterpret_cast<const uint64_t*>(&got);
+        for (size_t k = 0; k < sizeof(gs_counters) / 8; k++) dst[k] += src[k];
+    }
     return GS_OK;
 }
 

@@ -5,6 +5,11 @@ BVH.rs:69-90) for batches of caller rays on the device, through gs_query_rays (a
 own, csrc/device/query.hip): the closest hit with HitRecord's fields, or whether anything is hit
 at all.  Picking, visibility tests, depth / normal / material probes, baking, and "why does this
 pixel differ from the oracle" all start here.
+
+``RayQuery.radiance`` answers the other half of the per-pixel path, ``Camera::ray_color(ray, depth,
+world)`` (camera.rs:174-202), through gs_query_radiance (csrc/device/radiance.hip): the light that
+comes back along each caller ray, for cameras the reference does not have (``panorama_rays``,
+``ortho_rays``), light-map baking, probes, and replaying one pixel's path.
 """
 import ctypes as C
 
@@ -19,7 +24,9 @@ RAY_DTYPE = np.dtype([("o", "<f8", 3), ("d", "<f8", 3), ("time", "<f8"), ("tmin"
 HIT_DTYPE = np.dtype([("t", "<f8"), ("p", "<f8", 3), ("n", "<f8", 3), ("u", "<f8"), ("v", "<f8"), ("hit", "<u4"),
                       ("front", "<u4"), ("material", "<u4"), ("ref", "<u4"), ("inst", "<u4"), ("pad", "<u4"),
                       ("state", "<u8")])
+RADIANCE_DTYPE = np.dtype([("rgb", "<f8", 3), ("rays", "<u8"), ("state", "<u8")])
 assert RAY_DTYPE.itemsize == C.sizeof(N.gs_ray) == 72 and HIT_DTYPE.itemsize == C.sizeof(N.gs_ray_hit) == 104
+assert RADIANCE_DTYPE.itemsize == C.sizeof(N.gs_ray_radiance) == 40
 
 
 def pack_rays(rays):
@@ -54,6 +61,42 @@ def camera_rays(cam, time=0.0, tmin=0.001, tmax=np.finfo(np.float64).max):
     a[:, 0:3] = c
     a[:, 3:6] = ps - c
     a[:, 6], a[:, 7], a[:, 8] = time, tmin, tmax
+    return a
+
+
+def panorama_rays(center, width, height, time=0.0):
+    """An equirectangular camera at `center`: [height * width, 9] rays, row by row, with unit
+    directions over the full sphere through the texel centres of a width x height sky map.
+
+    The convention is HDRI::sample's (camera.rs:257-270) run backwards, in the sky map's own frame
+    (the background's rotation applied to nothing): pixel (row j, column i) looks along
+    (cos phi cos theta, cos phi sin theta, sin phi) with theta = ((i + 0.5) / width - 0.5) 2 pi and
+    phi = (0.5 - (j + 0.5) / height) pi -- z is up, row 0 is next to the +z pole, column 0 starts at
+    theta = -pi -- so that u = 0.5 + atan2(y, x) / 2 pi and v = 0.5 - asin(z) / pi name texel (i, j):
+    in an empty world under an unrotated width x height HDRI the radiance is the sky map itself."""
+    W, H = int(width), int(height)
+    j, i = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    theta = ((i.reshape(-1) + 0.5) / W - 0.5) * (2.0 * np.pi)
+    phi = (0.5 - (j.reshape(-1) + 0.5) / H) * np.pi
+    a = np.empty((W * H, 9), dtype=np.float64)
+    a[:, 0:3] = np.asarray(center, dtype=np.float64)
+    a[:, 3], a[:, 4], a[:, 5] = np.cos(phi) * np.cos(theta), np.cos(phi) * np.sin(theta), np.sin(phi)
+    a[:, 3:6] /= np.linalg.norm(a[:, 3:6], axis=1, keepdims=True)
+    a[:, 6], a[:, 7], a[:, 8] = time, 0.001, np.finfo(np.float64).max
+    return a
+
+
+def ortho_rays(corner, edge_u, edge_v, direction, width, height, time=0.0):
+    """An orthographic camera: [height * width, 9] parallel rays along `direction` (as given, not
+    normalised), row by row, from the cell centres corner + (i + 0.5) / width edge_u + (j + 0.5) /
+    height edge_v of a rectangle cut into width x height cells."""
+    W, H = int(width), int(height)
+    c, eu, ev = (np.asarray(v, dtype=np.float64) for v in (corner, edge_u, edge_v))
+    j, i = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    a = np.empty((W * H, 9), dtype=np.float64)
+    a[:, 0:3] = (c[None, :] + eu[None, :] * ((i.reshape(-1, 1) + 0.5) / W)) + ev[None, :] * ((j.reshape(-1, 1) + 0.5) / H)
+    a[:, 3:6] = np.asarray(direction, dtype=np.float64)
+    a[:, 6], a[:, 7], a[:, 8] = time, 0.001, np.finfo(np.float64).max
     return a
 
 
@@ -126,3 +169,29 @@ class RayQuery:
         """The first accepted hit of each ray's walk: `hit` equals closest()'s; the record is that
         hit's, not the nearest one's."""
         return self._run(rays, N.GS_QUERY_ANY, seed, counts)
+
+    def radiance(self, rays, samples=1, max_depth=50, seed=1, chunk=0, states=None, counters=False):
+        """Camera::ray_color(ray, max_depth, world) of each ray, `samples` samples each (the rays'
+        tmin / tmax are not read: every segment is tested over (0.001, f64::MAX)).  Sample s of ray i
+        draws from stream_seed(seed, i, s), or from states[i * samples + s] when `states` ([n *
+        samples] u64) is given.  A dict of arrays: sum [n, 3] f64 (the samples' colours added in
+        chunks of `chunk`, 0 = 16: the render's association), rgb = sum / samples, rays (world.hit
+        calls), state (the stream after the last sample); with counters=True also "counters", the
+        batch's totals as a dict (a render's counters; pixels stays 0)."""
+        a = pack_rays(rays)
+        n = len(a)
+        st = None
+        if states is not None:
+            st = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1)
+            if len(st) != n * int(samples):
+                raise ValueError("states must hold n * samples stream states")
+        out = np.zeros(n, dtype=RADIANCE_DTYPE)
+        cnt = N.gs_counters() if counters else None
+        N.check(N.lib.gs_query_radiance(self.dev, a.ctypes.data, n, samples, chunk, max_depth, seed,
+                                        st.ctypes.data if st is not None and len(st) else None, out.ctypes.data,
+                                        C.addressof(cnt) if counters else None))
+        res = {"sum": out["rgb"].copy(), "rgb": out["rgb"] / float(samples), "rays": out["rays"].copy(),
+               "state": out["state"].copy()}
+        if counters:
+            res["counters"] = cnt.as_dict()
+        return res

@@ -1026,6 +1026,57 @@ gs_status gs_query_rays_async(const gs_device_scene* scene, const gs_ray* d_rays
 gs_status gs_query_rays(const gs_device_scene* scene, const gs_ray* rays, int64_t n, int32_t mode, uint64_t seed,
                         gs_ray_hit* hits, uint32_t* counts /* nullable */);
 
+/* ---- Radiance queries: ray_color(ray, depth, world) for caller rays (additive, ABI 11) ----
+ * What the reference answers with `Camera::ray_color(&ray, max_depth, world)` (camera.rs:174-202),
+ * for a batch of rays and `samples` samples of each, in a kernel of its own: the other half of the
+ * per-pixel path, for any camera (panoramas, fisheye, orthographic, a measured lens), for baking
+ * and probes, and for replaying one pixel's path.  Sample s of ray i is ray_color(Ray(o, d, time),
+ * max_depth, world) with its stream started at stream_seed(seed, i, s) or, when
+ * d_states is given, at d_states[i * samples + s] -- a stream carried over from a closest query's
+ * `state`, or from the caller's own ray generator.  Every segment is tested over Interval(0.001,
+ * f64::MAX), as camera.rs:177 does: gs_ray.tmin and gs_ray.tmax are NOT read, so one ray buffer
+ * serves both kinds of query.  max_depth == 0 traces no ray: rgb = +0.0, rays = 0, state = the last
+ * sample's start state.
+ *
+ * A sample's colour takes the forward form: T = (1 a1) a2 ..., and a path
+ * that ends does so with T c -- c the sky's colour, the emitted colour, or 0 for an absorbed ray; a
+ * path that runs out of depth is black.  A ray's samples are cut into chunks of `chunk` consecutive
+ * samples (0: 16; the last may be short) and rgb = ((0 + C_0) + C_1) + ... with each C_k = ((0 + s)
+ * + s) + ... in sample order: the render's association, so the bits are a function of (ray, seed or
+ * states, samples, chunk, max_depth, scene) alone -- not of the batch's size, the ray's place in it
+ * or the scheduling.
+ *
+ * d_counters (nullable, accumulated into): the batch's totals in a render's meaning -- rays, the
+ * seven test counters, medium_tests, hits, image_texels, hdri_texels, noise_evals; paths receives
+ * n * samples; pixels is left alone.
+ *
+ * GS_ERR_ARG, before anything touches the device: a NULL scene, rays or out; n < 0; samples == 0;
+ * n * ceil(samples / chunk) >= 2^31; with more than one chunk per ray, a d_scratch that is NULL or
+ * smaller than gs_query_radiance_scratch_bytes (which is 0 for one chunk per ray: d_scratch may
+ * then be NULL); then a scene on another device.  n == 0 is GS_OK with no launch.  Any ray bits are
+ * accepted, as in gs_query_rays: the depth bound and the forward-only links end every path.  The
+ * async form takes device pointers and enqueues its launches on `stream`; d_scratch (256-byte
+ * alignment is not needed, 8 is) belongs to the call until they have run.  The synchronous form
+ * takes host arrays, allocates its own scratch and adds the totals to a host gs_counters. */
+typedef struct gs_ray_radiance {
+    double rgb[3];  /* the SUM over the ray's samples of ray_color, f64 (divide by samples for the mean) */
+    uint64_t rays;  /* world.hit calls of all its samples (camera.rs:177) */
+    uint64_t state; /* the stream after the last sample's path */
+} gs_ray_radiance; /* 40 B */
+int64_t gs_query_radiance_scratch_bytes(int64_t n, uint32_t samples, uint32_t chunk); /* -1: bad arguments */
+/* Test hook: the lanes of a wave that wait at the end of their walk before the wave shades them together,
+ * 1 .. 64 (0: the default, 24; others GS_ERR_ARG).  Process-wide.  Scheduling only: every choice returns
+ * the same bits. */
+gs_status gs_debug_set_radiance_batch(int32_t shade_batch);
+gs_status gs_query_radiance_async(const gs_device_scene* scene, const gs_ray* d_rays, int64_t n, uint32_t samples,
+                                  uint32_t chunk, uint32_t max_depth, uint64_t seed,
+                                  const uint64_t* d_states /* nullable */, gs_ray_radiance* d_out,
+                                  gs_counters* d_counters /* nullable */, void* d_scratch, int64_t scratch_bytes,
+                                  void* stream);
+gs_status gs_query_radiance(const gs_device_scene* scene, const gs_ray* rays, int64_t n, uint32_t samples,
+                            uint32_t chunk, uint32_t max_depth, uint64_t seed, const uint64_t* states /* nullable */,
+                            gs_ray_radiance* out, gs_counters* counters /* nullable */);
+
 /* Synchronous full-frame render on the current device: upload, render, copy back.
  * out_rgb: host buffer W*H*3 f32 (linear).  stats: host, nullable (counters, kernel and
  * render times, algorithmic bytes).  This is the one-call replacement for camera.rs:105-114:
