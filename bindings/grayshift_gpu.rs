@@ -173,6 +173,19 @@ pub struct gs_ray_radiance {
 }
 pub const GS_QUERY_CLOSEST: i32 = 0;
 pub const GS_QUERY_ANY: i32 = 1;
+/// A generated radiance query's ray generator: the kind, the image's dimensions, and what the kind
+/// reads -- a camera, or an origin and three axes (additive, ABI 11).  280 B.
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct gs_raygen {
+    pub kind: i32, pub width: i32, pub height: i32, pub pad: i32,
+    pub cam: gs_camera,
+    pub origin: [f64; 3],
+    pub axis: [[f64; 3]; 3],
+}
+pub const GS_GEN_CAMERA: i32 = 0;
+pub const GS_GEN_PANORAMA: i32 = 1;
+pub const GS_GEN_ORTHO: i32 = 2;
+pub const GS_GEN_HEMISPHERE: i32 = 3;
 
 /// An open views accumulation of the frame context (progressive views; additive, ABI 11).
 #[repr(C)] #[derive(Clone, Copy, Default)]
@@ -293,6 +306,16 @@ extern "C" {
     pub fn gs_query_radiance(scene: *const gs_device_scene, rays: *const gs_ray, n: i64, samples: u32, chunk: u32,
                              max_depth: u32, seed: u64, states: *const u64, out: *mut gs_ray_radiance,
                              counters: *mut gs_counters) -> gs_status;
+    /// Radiance queries whose rays a device generator draws from each sample's stream (ABI 11).
+    pub fn gs_query_radiance_gen_async(scene: *const gs_device_scene, gen: *const gs_raygen, d_points: *const gs_ray,
+                                       samples: u32, first_sample: u32, chunk: u32, max_depth: u32, seed: u64,
+                                       d_out: *mut gs_ray_radiance, d_counters: *mut gs_counters,
+                                       d_rays_out: *mut gs_ray, d_states_out: *mut u64, d_scratch: *mut c_void,
+                                       scratch_bytes: i64, stream: *mut c_void) -> gs_status;
+    pub fn gs_query_radiance_gen(scene: *const gs_device_scene, gen: *const gs_raygen, points: *const gs_ray,
+                                 samples: u32, first_sample: u32, chunk: u32, max_depth: u32, seed: u64,
+                                 out: *mut gs_ray_radiance, counters: *mut gs_counters, rays_out: *mut gs_ray,
+                                 states_out: *mut u64) -> gs_status;
     pub fn gs_ppm_max_bytes(width: i32, height: i32) -> i64;
     pub fn gs_ppm_scratch_bytes(width: i32, height: i32) -> i64;
     pub fn gs_ppm_encode_async(d_rgb8: *const u8, width: i32, height: i32, d_text: *mut c_char, text_capacity: i64,

@@ -16,7 +16,7 @@ _EXPORTS = {
     "render_multi": "renderer", "MultiRenderer": "renderer", "ProgressiveRenderer": "renderer",
     "AdaptiveRenderer": "renderer", "render_views": "renderer", "ViewsProgressiveRenderer": "renderer",
     "ViewsAdaptiveRenderer": "renderer", "render_views_adaptive": "renderer",
-    "RayQuery": "query", "camera_rays": "query", "panorama_rays": "query", "ortho_rays": "query",
+    "RayQuery": "query", "RayGen": "query", "camera_rays": "query", "panorama_rays": "query", "ortho_rays": "query",
     "SceneBuilder": "scene", "camera_spec": "scene", "fixed_spp": "scene", "sample_settings": "scene",
 }
 _SUBMODULES = {"scenes", "partition", "assets", "_native", "scene", "codeobj", "checkpoint", "query"}

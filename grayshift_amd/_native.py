@@ -257,6 +257,16 @@ class gs_ray_radiance(C.Structure):
     _fields_ = [("rgb", D3), ("rays", C.c_uint64), ("state", C.c_uint64)]
 
 
+GS_GEN_CAMERA, GS_GEN_PANORAMA, GS_GEN_ORTHO, GS_GEN_HEMISPHERE = 0, 1, 2, 3
+
+
+class gs_raygen(C.Structure):
+    """A generated radiance query's ray generator: the kind, the image's dimensions, and what the
+    kind reads -- a camera, or an origin and three axes.  280 B."""
+    _fields_ = [("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("pad", C.c_int32),
+                ("cam", gs_camera), ("origin", D3), ("axis", D3 * 3)]
+
+
 class gs_views_accum_info(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("n_views", C.c_uint32), ("chunk", C.c_uint32),
                 ("passes", C.c_uint32), ("tile_h", C.c_int32), ("counters", gs_counters)]
@@ -347,6 +357,10 @@ SIGNATURES = {
     "gs_query_radiance_async": (C.c_int32, [_P, _P, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P,
                                             _P, _P, C.c_int64, _P]),
     "gs_query_radiance": (C.c_int32, [_P, _P, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P, _P]),
+    "gs_query_radiance_gen_async": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P,
+                                                _P, _P, _P, _P, C.c_int64, _P]),
+    "gs_query_radiance_gen": (C.c_int32, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _P, _P,
+                                          _P, _P]),
     "gs_render": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64, _P,
                               C.POINTER(gs_stats)]),
     "gs_render_multi": (C.c_int32, [_P, C.POINTER(gs_camera), C.POINTER(gs_sample_settings), C.c_uint64,

@@ -45,7 +45,9 @@ SOURCES = [
 QUERY_SOURCE = os.path.join(HERE, "csrc", "device", "query.hip")
 # ... and the radiance-query kernels (ray_color for caller rays), the same library's second unit
 RADIANCE_SOURCE = os.path.join(HERE, "csrc", "device", "radiance.hip")
-QUERY_SOURCES = [QUERY_SOURCE, RADIANCE_SOURCE]
+# ... and the generated radiance queries (a ray drawn on the device for every sample), its third
+RAYGEN_SOURCE = os.path.join(HERE, "csrc", "device", "raygen.hip")
+QUERY_SOURCES = [QUERY_SOURCE, RADIANCE_SOURCE, RAYGEN_SOURCE]
 
 
 def query_lib(lib):

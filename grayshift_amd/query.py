@@ -10,6 +10,11 @@ pixel differ from the oracle" all start here.
 world)`` (camera.rs:174-202), through gs_query_radiance (csrc/device/radiance.hip): the light that
 comes back along each caller ray, for cameras the reference does not have (``panorama_rays``,
 ``ortho_rays``), light-map baking, probes, and replaying one pixel's path.
+
+``RayQuery.radiance_gen`` is that query with a ray drawn on the device for every sample, from the
+sample's own stream (gs_query_radiance_gen, csrc/device/raygen.hip): a ``RayGen`` names the
+generator -- the reference's thin-lens camera, a jittered panorama or orthographic camera, or
+cosine-weighted directions about caller points for baking -- and nothing is uploaded per sample.
 """
 import ctypes as C
 
@@ -98,6 +103,68 @@ def ortho_rays(corner, edge_u, edge_v, direction, width, height, time=0.0):
     a[:, 3:6] = np.asarray(direction, dtype=np.float64)
     a[:, 6], a[:, 7], a[:, 8] = time, 0.001, np.finfo(np.float64).max
     return a
+
+
+class RayGen:
+    """A device ray generator of RayQuery.radiance_gen (a gs_raygen and, for a hemisphere, its
+    points): item q = row q // width, column q % width of a width x height image, sample s drawn from
+    stream_seed(seed, q, first_sample + s).  The draws of each kind: include/grayshift_gpu.h."""
+
+    def __init__(self, raw, points=None):
+        self.raw = raw
+        self.points = points  # [n, 9] f64 (o = the point, d = the normal, time), GS_GEN_HEMISPHERE only
+
+    @property
+    def shape(self):
+        """(height, width) of the generator's image."""
+        if self.raw.kind == N.GS_GEN_CAMERA:
+            return self.raw.cam.image_height, self.raw.cam.image_width
+        return self.raw.height, self.raw.width
+
+    @staticmethod
+    def camera(cam):
+        """Camera::get_ray (camera.rs:204-221) of a gs_camera: the pixel's jitter, the defocus disk
+        when defocus_angle > 0, and the time draw -- the render's own camera rays."""
+        g = N.gs_raygen()
+        g.kind, g.width, g.height = N.GS_GEN_CAMERA, cam.image_width, cam.image_height
+        C.memmove(C.addressof(g.cam), C.addressof(cam), C.sizeof(N.gs_camera))
+        return RayGen(g)
+
+    @staticmethod
+    def panorama(center, w, h, axes=None):
+        """panorama_rays' equirectangular camera at `center`, jittered inside each texel, with a time
+        draw; axes: the rows x, y, z of the camera's frame in the world ([3, 3]; None: the world's)."""
+        g = N.gs_raygen()
+        g.kind, g.width, g.height = N.GS_GEN_PANORAMA, int(w), int(h)
+        g.origin[:] = [float(x) for x in center]
+        ax = np.eye(3) if axes is None else np.asarray(axes, dtype=np.float64).reshape(3, 3)
+        for k in range(3):
+            g.axis[k][:] = [float(x) for x in ax[k]]
+        return RayGen(g)
+
+    @staticmethod
+    def ortho(corner, edge_u, edge_v, direction, w, h):
+        """ortho_rays' orthographic camera, jittered inside each cell, with a time draw."""
+        g = N.gs_raygen()
+        g.kind, g.width, g.height = N.GS_GEN_ORTHO, int(w), int(h)
+        g.origin[:] = [float(x) for x in corner]
+        for k, v in enumerate((edge_u, edge_v, direction)):
+            g.axis[k][:] = [float(x) for x in v]
+        return RayGen(g)
+
+    @staticmethod
+    def hemisphere(points, normals, time=0.0):
+        """Cosine-weighted directions about `normals` from `points` ([n, 3] each), at `time` (a
+        scalar or [n]): Lambertian::scatter's direction (material.rs:52-53).  A 1 x n image."""
+        p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        a = np.zeros((len(p), 9), dtype=np.float64)
+        a[:, 0:3] = p
+        a[:, 3:6] = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
+        a[:, 6] = np.broadcast_to(np.asarray(time, dtype=np.float64), (len(p),))
+        a[:, 7], a[:, 8] = 0.001, np.finfo(np.float64).max
+        g = N.gs_raygen()
+        g.kind, g.width, g.height = N.GS_GEN_HEMISPHERE, len(p), 1
+        return RayGen(g, a)
 
 
 class RayQuery:
@@ -194,4 +261,33 @@ class RayQuery:
                "state": out["state"].copy()}
         if counters:
             res["counters"] = cnt.as_dict()
+        return res
+
+    def radiance_gen(self, gen, samples, max_depth=50, seed=1, chunk=0, first_sample=0, counters=False, emit=False):
+        """Camera::ray_color along a ray the device draws for every sample of every item of `gen` (a
+        RayGen), samples [first_sample, first_sample + samples) of the (item, sample) streams of
+        `seed`.  A dict of arrays: sum [H, W, 3] f64 (the samples' colours added in chunks of `chunk`,
+        0 = 16), rgb = sum / samples, rays [H, W] (world.hit calls), state [H, W] (the stream after the
+        last sample); with counters=True also "counters"; with emit=True also "gen_rays" [H * W *
+        samples, 9] and "gen_states" [H * W * samples]: each sample's generated ray and the stream
+        right after its generation, which radiance(gen_rays, samples=1, states=gen_states) retraces."""
+        h, w = gen.shape
+        n = max(h, 0) * max(w, 0)
+        samples = int(samples)
+        out = np.zeros(n, dtype=RADIANCE_DTYPE)
+        cnt = N.gs_counters() if counters else None
+        rays = np.zeros((n * samples, 9), dtype=np.float64) if emit else None
+        states = np.zeros(n * samples, dtype=np.uint64) if emit else None
+        pts = gen.points
+        N.check(N.lib.gs_query_radiance_gen(self.dev, C.addressof(gen.raw), pts.ctypes.data if pts is not None else None,
+                                            samples, first_sample, chunk, max_depth, seed, out.ctypes.data,
+                                            C.addressof(cnt) if counters else None,
+                                            rays.ctypes.data if emit and rays.size else None,
+                                            states.ctypes.data if emit and states.size else None))
+        res = {"sum": out["rgb"].reshape(h, w, 3).copy(), "rgb": out["rgb"].reshape(h, w, 3) / float(samples),
+               "rays": out["rays"].reshape(h, w).copy(), "state": out["state"].reshape(h, w).copy()}
+        if counters:
+            res["counters"] = cnt.as_dict()
+        if emit:
+            res["gen_rays"], res["gen_states"] = rays, states
         return res

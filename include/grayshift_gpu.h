@@ -1077,6 +1077,77 @@ gs_status gs_query_radiance(const gs_device_scene* scene, const gs_ray* rays, in
                             uint32_t chunk, uint32_t max_depth, uint64_t seed, const uint64_t* states /* nullable */,
                             gs_ray_radiance* out, gs_counters* counters /* nullable */);
 
+/* ---- Radiance queries with device ray generators (additive, ABI 11) ----
+ * gs_query_radiance traces the same ray for every sample of an item.  The reference's Camera::sample
+ * (camera.rs:138-141) draws the ray of every sample from the sample's own stream before it calls
+ * ray_color, and so do these entries: jitter inside the pixel, a point on the defocus disk, a time,
+ * a cosine-weighted direction over a texel's hemisphere -- made on the device at the start of each
+ * sample, with nothing uploaded per sample.
+ *
+ * Items: n = width * height, row-major -- item q is row j = q / width, column i = q % width.
+ * GS_GEN_CAMERA takes both dimensions from gen->cam (gen->width and gen->height are not read);
+ * GS_GEN_HEMISPHERE has height = 1 and width = n points.  Sample s of item q draws from
+ * stream_seed(seed, q, first_sample + s), the render's (pixel, sample) stream, in this order (wy =
+ * one f64 draw; every sum and product as written, left to right):
+ *   GS_GEN_CAMERA      Camera::get_ray (camera.rs:204-221): offx = wy - 0.5, offy = wy - 0.5; si =
+ *                      (double)i + offx, sj = (double)j + offy; ps = (starting_pixel_pos +
+ *                      pixel_delta_u * si) + pixel_delta_v * sj; the origin is `center`, or with
+ *                      defocus_angle > 0: draw dx = wy * 2 - 1, dy = wy * 2 - 1 until dx dx + dy dy
+ *                      < 1, origin = (center + defocus_disk_u * dx) + defocus_disk_v * dy; d = ps -
+ *                      origin; time = wy, the last draw.
+ *   GS_GEN_PANORAMA    offx, offy, si, sj as above; theta = ((si + 0.5) / width - 0.5) * (2 pi),
+ *                      phi = (0.5 - (sj + 0.5) / height) * pi, dl = unit((cos phi cos theta, cos phi
+ *                      sin theta, sin phi)); d = (axis[0] * dl.x + axis[1] * dl.y) + axis[2] * dl.z,
+ *                      o = origin; time = wy.  Identity axes, no jitter: query.panorama_rays.
+ *   GS_GEN_ORTHO       offx, offy, si, sj as above; o = (origin + axis[0] * ((si + 0.5) / width)) +
+ *                      axis[1] * ((sj + 0.5) / height) (axis[0], axis[1]: the rectangle's edges), d =
+ *                      axis[2] as given; time = wy.  No jitter: query.ortho_rays.
+ *   GS_GEN_HEMISPHERE  p = d_points[q].o, nrm = d_points[q].d, time = d_points[q].time (tmin, tmax:
+ *                      not read); OrthonormalBasis::new(nrm) (ONB.rs:10-23); r1 = wy, r2 = wy and
+ *                      random_cosine_direction (util.rs:48-60, its r2^(1/4) kept) as (x, y, z); o =
+ *                      p, d = unit(u * x + v * y + w * z): Lambertian::scatter's direction
+ *                      (material.rs:52-53).  No time draw.
+ * Then ray_color(Ray(o, d, time), max_depth, world) goes on from the stream the generator left.
+ * Any bits are accepted in gen and the points, as everywhere in the queries.
+ *
+ * d_out[q]: the gs_ray_radiance of gs_query_radiance -- the f64 sum in chunks of `chunk` (0: 16) in
+ * sample order, the world.hit calls, the stream after the last sample.  max_depth == 0 draws nothing
+ * and traces nothing: rgb = +0.0, rays = 0, state = the last sample's start state, and nothing is
+ * written to d_rays_out / d_states_out.  Otherwise d_rays_out[q * samples + s] (nullable) receives
+ * the generated ray, with tmin = 0.001 and tmax = f64::MAX, and d_states_out[q * samples + s]
+ * (nullable) the stream right after the generation: gs_query_radiance's d_states indexing, so at
+ * samples = 1 over n * samples rays the pair gives the same paths.  d_counters: as gs_query_radiance.
+ * A progressive caller adds calls over [first_sample, first_sample + samples) ranges.
+ *
+ * GS_ERR_ARG, before anything touches the device: a NULL scene, gen or out; a kind outside the
+ * four; a dimension below 1; GS_GEN_HEMISPHERE without points (points given with another kind are
+ * ignored); samples == 0; first_sample + samples > 2^32; n * ceil(samples / chunk) >= 2^31; a
+ * scratch that is NULL or smaller than gs_query_radiance_scratch_bytes(n, samples, chunk) where that
+ * is not 0; then a scene on another device.  Concurrency is the radiance queries'.  The synchronous
+ * form takes host arrays (rays_out, states_out: n * samples each; GS_ERR_ARG when that many gs_ray
+ * exceed half the address space) and allocates its own scratch. */
+#define GS_GEN_CAMERA 0
+#define GS_GEN_PANORAMA 1
+#define GS_GEN_ORTHO 2
+#define GS_GEN_HEMISPHERE 3
+typedef struct gs_raygen {
+    int32_t kind, width, height, pad;
+    gs_camera cam;     /* GS_GEN_CAMERA */
+    double origin[3];  /* PANORAMA: the eye; ORTHO: the rectangle's corner */
+    double axis[3][3]; /* PANORAMA: the frame's x, y, z (z up); ORTHO: edge_u, edge_v, the direction */
+} gs_raygen; /* 280 B */
+gs_status gs_query_radiance_gen_async(const gs_device_scene* scene, const gs_raygen* gen /* host */,
+                                      const gs_ray* d_points /* GS_GEN_HEMISPHERE only */, uint32_t samples,
+                                      uint32_t first_sample, uint32_t chunk, uint32_t max_depth, uint64_t seed,
+                                      gs_ray_radiance* d_out, gs_counters* d_counters /* nullable */,
+                                      gs_ray* d_rays_out /* nullable */, uint64_t* d_states_out /* nullable */,
+                                      void* d_scratch, int64_t scratch_bytes, void* stream);
+gs_status gs_query_radiance_gen(const gs_device_scene* scene, const gs_raygen* gen,
+                                const gs_ray* points /* GS_GEN_HEMISPHERE only */, uint32_t samples,
+                                uint32_t first_sample, uint32_t chunk, uint32_t max_depth, uint64_t seed,
+                                gs_ray_radiance* out, gs_counters* counters /* nullable */,
+                                gs_ray* rays_out /* nullable */, uint64_t* states_out /* nullable */);
+
 /* Synchronous full-frame render on the current device: upload, render, copy back.
  * out_rgb: host buffer W*H*3 f32 (linear).  stats: host, nullable (counters, kernel and
  * render times, algorithmic bytes).  This is the one-call replacement for camera.rs:105-114:
